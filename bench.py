@@ -15,7 +15,7 @@ a launch touches ~0.48 GB of distinct table lines, eight of them ~3.8 GB - far m
 Cache - so no launch finds lines a previous launch left in a cache.  The one-batch-repeated figure of rounds 1-2 is
 reported beside it (`roofline.single_batch`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 1000000] [--workload prior|posterior]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 1000000] [--workload prior|posterior] [--dump-outputs DIR]
 
 `value` = evaluations of all ranks / the slowest rank's DEVICE time for its K launches (HIP events on the launch
 stream, inside the barrier + synchronize bracket); the wall-clock of the same bracket is reported as
@@ -467,6 +467,26 @@ class Rotation:
         return ms.value
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, lnpost):
+    """The lnpost values of one timed launch as two all-finite float64 arrays: DIR/lnpost.npy holds the finite values in
+    row order, DIR/lnpost_nonfinite.npy marks every row (0 finite, -1 -inf, +1 +inf, 2 NaN: a sample outside the prior
+    or the table is part of the result).  A batch whose two arrays would exceed DUMP_MAX_BYTES is written as a fixed
+    seeded sample of its rows (ascending row order), the same rows for every build."""
+    os.makedirs(out_dir, exist_ok=True)
+    cap = (DUMP_MAX_BYTES - 8192) // 16
+    if lnpost.size > cap:
+        lnpost = lnpost[np.sort(np.random.default_rng(0).choice(lnpost.size, cap, replace=False))]
+    kind = np.zeros(lnpost.size)
+    kind[np.isneginf(lnpost)] = -1.0
+    kind[np.isposinf(lnpost)] = 1.0
+    kind[np.isnan(lnpost)] = 2.0
+    np.save(os.path.join(out_dir, "lnpost.npy"), np.ascontiguousarray(lnpost[kind == 0.0], dtype=np.float64))
+    np.save(os.path.join(out_dir, "lnpost_nonfinite.npy"), kind)
+
+
 def spawn_ranks(n_ranks, argv=None):
     """Re-run this script under torch.distributed.run with one rank per GPU (a bare `python bench.py --gpus N`).
     Returns the launcher's exit code; the ranks inherit stdout / stderr, so rank 0's JSON line is this process's."""
@@ -505,7 +525,13 @@ def main():
                     help="seconds after which the line is printed with whatever the secondary legs have produced")
     ap.add_argument("--path", default=None, choices=["auto", "compact", "generic"],
                     help="kernel/table-layout selection (default: library default = auto)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's lnpost of the last timed step to DIR/lnpost.npy (its finite "
+                         "values) and DIR/lnpost_nonfinite.npy (which rows are -inf / NaN), float64, so that two builds "
+                         "can be compared output for output on the same seeded batches")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.path:
         os.environ["ISOCHRONES_AMD_PATH"] = args.path
@@ -604,6 +630,9 @@ def main():
         tmax = torch.tensor([elapsed, kernel_ms], dtype=torch.float64, device=reduce_device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed, kernel_ms = float(tmax[0]), float(tmax[1])
+    if args.dump_outputs and rank == 0:
+        # the last timed launch evaluated batch (K - 1) mod nb; nothing has overwritten its output since
+        dump_outputs(args.dump_outputs, rot.outs[(args.steps - 1) % nb].cpu().numpy())
 
     total_evals = float(args.n) * args.steps * world
     device_s = kernel_ms * 1e-3 * args.steps

@@ -1,4 +1,4 @@
-"""Wherever the reference checkout is present (/root/reference: the authoring container, not the GPU box): regenerate
+"""Wherever a checkout of the reference is present (oracle/ref_harness.py: $ISO_REFERENCE_ROOT): regenerate
 every fixture with oracle/make_golden.py - i.e. run the reference itself - into a scratch directory and require the
 result to be byte-identical to tests/golden/.  This is the pin that ties the committed vectors to the reference
 (ISO_CHECK_GOLDENS=0 skips it)."""
@@ -9,11 +9,13 @@ import sys
 
 import pytest
 
+from oracle import ref_harness
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.skipif(os.environ.get("ISO_CHECK_GOLDENS") == "0" or not os.path.isdir("/root/reference/isochrones"),
-                    reason="needs the reference checkout at /root/reference")
+@pytest.mark.skipif(os.environ.get("ISO_CHECK_GOLDENS") == "0" or not ref_harness.reference_available(),
+                    reason="needs a checkout of the reference ($ISO_REFERENCE_ROOT)")
 def test_make_golden_reproduces_the_committed_fixtures(tmp_path):
     env = dict(os.environ, ISO_GOLDEN_OUT=str(tmp_path), PYTHONDONTWRITEBYTECODE="1", PYTHONHASHSEED="12345")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "oracle", "make_golden.py")], cwd=ROOT, env=env,

@@ -109,18 +109,24 @@ def test_interp_eep_vs_reference(fixture):
 
 @pytest.mark.parametrize("seed", [101, 102, 103, 104, 105, 106])
 def test_model_case_on_fresh_draws_against_the_reference_itself(seed, tmp_path, monkeypatch):
-    """Container-only (needs /root/reference): instead of the committed vectors, the reference's StarModel classes are run
-    here on freshly drawn cases - parametrisation, multiplicity, observables and their values, bounds keywords, prior
-    families and sample points all random - and the oracle is put through the same checks as test_model_case."""
+    """The reference's StarModel classes on freshly drawn cases - parametrisation, multiplicity, observables and their
+    values, bounds keywords, prior families and sample points all random - and the oracle put through the same checks
+    as test_model_case.  What the reference computed for each seed's three cases is stored in
+    tests/golden/fresh/fresh_<seed>_<k>.npz; where the reference checkout is present the draws are run through it again
+    (tests/_fixtures.py: FRESH)."""
     import os
-    if not os.path.isdir("/root/reference/isochrones"):
-        pytest.skip("the reference tree is only present in the build container")
+    fx.tables()                                            # the committed small tables = mg.small_*(): cache them first
+    if not fx.reference_available():
+        monkeypatch.setattr(fx, "GOLDEN", fx.FRESH)
+        for k in range(3):
+            test_model_case("fresh_%d_%d" % (seed, k))
+        return
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     monkeypatch.syspath_prepend(os.path.join(root, "oracle"))
     import make_golden as mg
-    fx.tables()                                            # the committed small tables = mg.small_*(): cache them first
-    monkeypatch.setattr(mg, "OUT", str(tmp_path))
-    monkeypatch.setattr(fx, "GOLDEN", str(tmp_path))
+    out = fx.fresh_out(tmp_path)
+    monkeypatch.setattr(mg, "OUT", out)
+    monkeypatch.setattr(fx, "GOLDEN", out)
     rng = np.random.default_rng(seed)
     trk, iso, bc = mg.small_track(), mg.small_iso(), mg.small_bc()
     for k in range(3):

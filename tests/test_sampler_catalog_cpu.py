@@ -404,10 +404,12 @@ def test_checkpoint_digest_follows_the_start_point_method(monkeypatch):
     assert a != _shard_fingerprint(cat, np.arange(5), 1, dict(nwalkers=32), None_IC())
 
 
-# ---- eight ranks: the shape of the driver's scaling run (scripts/batch_starfit:60-62) -----------------------------
-def _world8_worker(rank, world, port, n_stars, out_dir):
-    """What one rank of `bench.py --gpus 8` does around its kernels: receive the tables from rank 0, fit its share of a
-    10^4-star catalog (star i -> rank (i + 1) % 8), meet the others in ONE all-gather.  Rank 5's fit fails."""
+# ---- four ranks: the shape of the driver's multi-GPU scaling run (scripts/batch_starfit:60-62) ------------------
+# (four ranks, not the eight of an 8-GPU run: where the suite runs on a shared GPU, the ranks next to this pytest process
+# count against the six processes a GPU admits)
+def _world4_worker(rank, world, port, n_stars, out_dir):
+    """What one rank of `bench.py --gpus 4` does around its kernels: receive the tables from rank 0, fit its share of a
+    10^4-star catalog (star i -> rank (i + 1) % 4), meet the others in ONE all-gather.  Rank 2's fit fails."""
     sys.path.insert(0, ROOT)
     import warnings
     import pandas as pd
@@ -428,7 +430,7 @@ def _world8_worker(rank, world, port, n_stars, out_dir):
 
     def fit(catalog, ic_, indices, N=1, **kw):
         seen.extend(int(i) for i in indices)
-        if rank == 5:
+        if rank == 2:
             raise RuntimeError("HIP error on this rank")
         rows = np.zeros((len(indices), 3 * (N + 4) + 3))
         rows[:, 0] = np.asarray(indices) * 2.0 + 1.0
@@ -440,9 +442,9 @@ def _world8_worker(rank, world, port, n_stars, out_dir):
         warnings.simplefilter("always")
         res = ia_.fit_catalog(cat, ic, N=1, fit_fn=fit)
     assert seen == [int(i) for i in mine]
-    assert any("rank 5" in str(x.message) for x in w)
+    assert any("rank 2" in str(x.message) for x in w)
     assert res.attrs["timings"]["world"] == world and res.attrs["timings"]["stars_of_this_rank"] == len(mine)
-    if rank in (0, 5, 7):
+    if rank in (0, 2, 3):
         res.to_pickle(os.path.join(out_dir, "res%d.pkl" % rank))
         np.save(os.path.join(out_dir, "grid%d.npy" % rank), ic.model_grid.interp.grid)
         with open(os.path.join(out_dir, "err%d.txt" % rank), "w") as f:
@@ -451,23 +453,23 @@ def _world8_worker(rank, world, port, n_stars, out_dir):
     dist.destroy_process_group()
 
 
-def test_eight_ranks_broadcast_fit_and_gather_with_uneven_shards_and_one_failing_rank(tmp_path):
-    """World size 8 on gloo: the rank count of the driver's scaling run, a catalog whose size 8 does not divide (10 003
-    stars: five ranks get 1 250, three get 1 251), one rank whose fit raises.  Every rank ends with the same table; the
-    failing rank's stars are NaN / ok = 0, everyone else's arrive; nobody hangs."""
+def test_four_ranks_broadcast_fit_and_gather_with_uneven_shards_and_one_failing_rank(tmp_path):
+    """World size 4 on gloo, a catalog whose size 4 does not divide (10 003 stars: one rank gets 2 500, three get
+    2 501), one rank whose fit raises.  Every rank ends with the same table; the failing rank's stars are NaN / ok = 0,
+    everyone else's arrive; nobody hangs."""
     import pandas as pd
     import torch.multiprocessing as mp
     n = 10_003
-    mp.spawn(_world8_worker, args=(8, _free_port(), n, str(tmp_path)), nprocs=8, join=True)
-    r0, r5, r7 = (pd.read_pickle(tmp_path / ("res%d.pkl" % r)) for r in (0, 5, 7))
-    assert r0.equals(r5) and r0.equals(r7) and len(r0) == n
-    owner = (np.arange(n) + 1) % 8                              # batch_starfit's rule: awk 'NR % NPROCS == TASK', NR = i + 1
-    assert sorted(np.bincount(owner)) == [1250] * 5 + [1251] * 3
-    ok = owner != 5
+    mp.spawn(_world4_worker, args=(4, _free_port(), n, str(tmp_path)), nprocs=4, join=True)
+    r0, r2, r3 = (pd.read_pickle(tmp_path / ("res%d.pkl" % r)) for r in (0, 2, 3))
+    assert r0.equals(r2) and r0.equals(r3) and len(r0) == n
+    owner = (np.arange(n) + 1) % 4                              # batch_starfit's rule: awk 'NR % NPROCS == TASK', NR = i + 1
+    assert sorted(np.bincount(owner)) == [2500] + [2501] * 3
+    ok = owner != 2
     assert np.array_equal(r0["ok"].values, ok.astype(float))
     assert np.array_equal(r0.iloc[ok, 0].values, np.flatnonzero(ok) * 2.0 + 1.0)
     assert np.array_equal(r0["lnpost_max"].values[ok], owner[ok].astype(float))
     assert np.isnan(r0.iloc[~ok, :-1].values).all()
-    for r in (0, 5, 7):
-        assert open(tmp_path / ("err%d.txt" % r)).read() == "[5]"
+    for r in (0, 2, 3):
+        assert open(tmp_path / ("err%d.txt" % r)).read() == "[2]"
         assert np.array_equal(np.load(tmp_path / ("grid%d.npy" % r)), np.load(tmp_path / "grid0.npy"), equal_nan=True)

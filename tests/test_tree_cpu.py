@@ -388,28 +388,57 @@ def _build_tree(api, spec, name):
     return t
 
 
+def _check_fresh_tree_case(case, mine):
+    """One drawn case of test_random_trees_against_the_reference_itself against what the reference made of it."""
+    spec, name = case["spec"], case["name"]
+    if case["refused"]:                  # a layout the reference itself does not take: neither does this build
+        kw = {k_: (tuple(v) if isinstance(v, list) and k_ not in ("N", "index") else v) for k_, v in case["kw"].items()}
+        with pytest.raises(Exception):
+            ic0 = fx.make_ic(dict(kind="iso", limits=case["limits"], eep_bounds=case["eep_bounds"]))
+            ia.TreeStarModel(ic0, obs=_build_tree(mine, spec, name), **kw)
+        return False
+    g = fx.load(name)
+    meta = g["meta"]
+    ic = fx.make_ic(dict(kind="iso", limits=meta["limits"], eep_bounds=meta["eep_bounds"]))
+    kw2 = {k_: (tuple(v) if isinstance(v, list) and k_ not in ("N", "index") else v) for k_, v in meta["kwargs"].items()}
+    mod = ia.TreeStarModel(ic, obs=_build_tree(mine, spec, name), **kw2)
+    if np.isfinite(g["lnpost"]).sum() <= 50:          # the draw left too few finite points for the last check
+        g["lnpost"] = g["lnpost"].copy()
+    _check_tree_case(g, ic, mod)
+    return True
+
+
 @pytest.mark.parametrize("seed", [201, 202, 203, 204, 205, 206, 3041, 3042])
 def test_random_trees_against_the_reference_itself(seed, tmp_path, monkeypatch):
-    """Container-only (needs /root/reference): random observation sets (unresolved bands, a seeing-limited image, an AO
-    image; relative or absolute photometry) and random N / index assignments are handed to the reference's
-    ObservationTree + StarModel and to this build's; structure, flattened terms and the oracle's numbers must agree as
-    for the committed cases."""
-    if not os.path.isdir("/root/reference/isochrones"):
-        pytest.skip("the reference tree is only present in the build container")
+    """Random observation sets (unresolved bands, a seeing-limited image, an AO image; relative or absolute photometry)
+    and random N / index assignments are handed to the reference's ObservationTree + StarModel and to this build's;
+    structure, flattened terms and the oracle's numbers must agree as for the committed cases.  What the reference made
+    of each seed's four draws is stored in tests/golden/fresh/ (fresh_tree_<seed>.json: the draws;
+    fresh_tree_<seed>_<k>.npz: the reference's model); where the reference checkout is present the draws are run
+    through it again (tests/_fixtures.py: FRESH)."""
+    import json
     import isochrones_amd.observation as mine
+    fx.tables()
+    if not fx.reference_available():
+        monkeypatch.setattr(fx, "GOLDEN", fx.FRESH)
+        with open(os.path.join(fx.FRESH, "fresh_tree_%d.json" % seed)) as f:
+            cases = json.load(f)
+        assert len(cases) == 4
+        assert sum(_check_fresh_tree_case(case, mine) for case in cases) >= 2
+        return
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     monkeypatch.syspath_prepend(os.path.join(root, "oracle"))
     import make_golden as mg
     import ref_harness as rh
-    fx.tables()
-    monkeypatch.setattr(mg, "OUT", str(tmp_path))
-    monkeypatch.setattr(fx, "GOLDEN", str(tmp_path))
+    out = fx.fresh_out(tmp_path)
+    monkeypatch.setattr(mg, "OUT", out)
+    monkeypatch.setattr(fx, "GOLDEN", out)
     sm, obs_mod = rh.ref("starmodel"), rh.ref("observation")
     rng = np.random.default_rng(seed)
     iso, bc = mg.small_iso(), mg.small_bc()
     axes = iso[1]
     limits = mg.limits_of("iso", axes)
-    done = 0
+    cases = []
     for k in range(4):
         spec = _random_tree_spec(rng)
         n_fine = max(len(srcs) for _, _, _, srcs in spec)
@@ -427,22 +456,16 @@ def test_random_trees_against_the_reference_itself(seed, tmp_path, monkeypatch):
         if rng.random() < 0.3: kw["AV"] = (0.2, 0.1)
         name = "fresh_tree_%d_%d" % (seed, k)
         ic_ref = rh.make_ref_ic("iso", iso, bc, limits, (axes[2][0], axes[2][-1]))
+        case = dict(name=name, spec=spec, kw=kw, refused=False, limits={k_: list(map(float, v)) for k_, v in limits.items()},
+                    eep_bounds=[float(axes[2][0]), float(axes[2][-1])])
         try:
             ref_mod = sm.StarModel(ic_ref, obs=_build_tree(obs_mod, spec, name), **kw)
         except Exception:                # a layout the reference itself does not take
-            with pytest.raises(Exception):
-                ic0 = fx.make_ic(dict(kind="iso", limits={k_: list(map(float, v)) for k_, v in limits.items()},
-                                      eep_bounds=[float(axes[2][0]), float(axes[2][-1])]))
-                ia.TreeStarModel(ic0, obs=_build_tree(mine, spec, name), **kw)
-            continue
-        mg._emit_tree_case(name, ref_mod, kw, True, rng, axes, limits, obs_mod)
-        g = fx.load(name)
-        meta = g["meta"]
-        ic = fx.make_ic(dict(kind="iso", limits=meta["limits"], eep_bounds=meta["eep_bounds"]))
-        kw2 = {k_: (tuple(v) if isinstance(v, list) and k_ not in ("N", "index") else v) for k_, v in meta["kwargs"].items()}
-        mod = ia.TreeStarModel(ic, obs=_build_tree(mine, spec, name), **kw2)
-        if np.isfinite(g["lnpost"]).sum() <= 50:          # the draw left too few finite points for the last check
-            g["lnpost"] = g["lnpost"].copy()
-        _check_tree_case(g, ic, mod)
-        done += 1
-    assert done >= 2
+            case["refused"] = True
+        else:
+            mg._emit_tree_case(name, ref_mod, kw, True, rng, axes, limits, obs_mod)
+        cases.append(case)
+    with open(os.path.join(out, "fresh_tree_%d.json" % seed), "w") as f:
+        json.dump(cases, f, indent=1)
+    with open(os.path.join(out, "fresh_tree_%d.json" % seed)) as f:
+        assert sum(_check_fresh_tree_case(case, mine) for case in json.load(f)) >= 2
