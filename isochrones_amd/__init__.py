@@ -15,5 +15,6 @@ from .catalog import (StarCatalog, CatalogPosterior, fit_catalog, synthetic_cata
                       broadcast_interpolator)
 from . import priors, grids, ingest, mist, nested, ini, persist, utils
 from .starfit import starfit, batch_starfit
+from .cluster import StarClusterModel, simulate_cluster
 
 __version__ = "0.1.0"

@@ -1,0 +1,415 @@
+"""Star clusters: one age, [Fe/H], distance, extinction, IMF slope, mass-ratio slope and binary fraction fitted to a whole
+table of member stars (reference: isochrones/cluster.py:182-477, cluster_utils.py).
+
+The per-EEP columns of every parameter row come from the device interpolators (``interp_device`` / ``interp_mag_device``
+over ``[rows x EEPs]`` points); the half-filled (primary EEP, secondary EEP) grid of every member star, its two trapezoid
+integrals and the sum over stars run in libiso_cluster.so (include/isochrones_amd_cluster.h).  Priors are seven scalars
+per row and are evaluated on the host.  Deviations from the reference ("Star clusters"): the property term
+is read in its documented ``[star, eep]`` layout, ``bounds()`` falls back to finite boxes for gamma and feh, ``set_prior``
+works."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from . import device as dev
+from . import priors as P
+from .catalog import StarCatalog
+from .starmodel import _NestedFitMixin
+
+_ROOT_2PI = math.sqrt(2.0 * math.pi)
+#: device bytes one chunk of rows may hold (columns, interpolation outputs, the inner-integral scratch)
+DEFAULT_CHUNK_BYTES = 256 << 20
+#: points per interpolation call (below the interpolation library's 1 024-point switch to its packed-table kernels)
+INTERP_SLICE = 1000
+
+
+def _lnpdf_vec(pr, x):
+    """``pr.lnpdf`` of every element of ``x`` - vectorised for this package's own families, element by element for any
+    other ``Prior`` (a user's subclass, a foreign object with ``lnpdf``)."""
+    x = np.asarray(x, dtype=float)
+    t = type(pr)
+    with np.errstate(all="ignore"):
+        if t is P.GaussianPrior:
+            z = (x - pr.mean) / pr.sigma
+            out = -(z * z) / 2.0 - math.log(_ROOT_2PI) - math.log(pr.sigma) - pr.lognorm
+            if pr.bounded:
+                out = np.where((x < pr.bounds[0]) | (x > pr.bounds[1]), -np.inf, out)
+            return out
+        if t is P.PowerLawPrior:
+            lo, hi = pr.bounds
+            out = np.log(pr._C()) + pr.alpha * np.log(x)
+            return np.where((x < lo) | (x > hi), -np.inf, out)
+        if t in (P.FlatPrior, P.FlatLogPrior, P.FehPrior):           # Prior.lnpdf: log(pdf), -inf where pdf is 0
+            p = pr.pdf_array(x)
+            out = np.where(p != 0, np.log(np.where(p != 0, p, 1.0)), -np.inf)
+            if pr.bounded:
+                out = np.where((x < pr.bounds[0]) | (x > pr.bounds[1]), -np.inf, out)
+            return out
+    return P.lnpdf_array(pr, x)
+
+
+class StarClusterModel(_NestedFitMixin):
+    """reference: cluster.py:182-412.  ``stars`` is a :class:`StarCatalog` or a DataFrame (``catalog_kwargs`` go to
+    the catalog).  ``lnprior`` / ``lnlike`` / ``lnpost`` take a 7-vector (-> float), a numpy ``[P, 7]`` array (-> numpy)
+    or a CUDA ``[P, 7]`` tensor (-> CUDA tensor); batches are evaluated in chunks of ``chunk_rows`` rows (default: as
+    many as fit in :data:`DEFAULT_CHUNK_BYTES` of device memory)."""
+
+    param_names = ("age", "feh", "distance", "AV", "alpha", "gamma", "fB")
+
+    def __init__(self, ic, stars, name="", halo_fraction=0.5, max_AV=1.0, max_distance=50000, use_emcee=False,
+                 eep_bounds=None, mass_bounds=None, minq=0.1, chunk_rows=None, **catalog_kwargs):
+        if getattr(ic, "eep_replaces", None) != "mass":
+            raise ValueError("StarClusterModel needs an isochrone grid (eep, age, feh); %s is parametrised by mass"
+                             % type(ic).__name__)
+        ci = ic.model_grid.interp.column_index
+        for col in ("initial_mass", "dm_deep"):
+            if col not in ci:
+                raise ValueError("the isochrone table lacks the column %r" % col)
+        self._ic = ic
+        if not isinstance(stars, StarCatalog):
+            stars = StarCatalog(stars, **catalog_kwargs)
+        self.stars = stars
+        if not 1 <= len(self.bands) <= 32:
+            raise ValueError("a cluster model needs 1 to 32 bands (got %d)" % len(self.bands))
+        if len(self.props) > 8:
+            raise ValueError("at most 8 further properties")
+        for q in self.props:
+            if q != "parallax" and q not in ci:
+                raise ValueError("property %r is neither parallax nor a column of the model table" % q)
+        self._priors = {
+            "age": P.FlatLogPrior((6, 10.15)),
+            "feh": P.FehPrior(halo_fraction=halo_fraction),
+            "AV": P.FlatPrior((0, max_AV)),
+            "distance": P.PowerLawPrior(2.0, (0, max_distance)),
+            "alpha": P.FlatPrior((-4, -1)),
+            "gamma": P.GaussianPrior(0.3, 0.1),
+            "fB": P.FlatPrior((0.0, 0.6)),
+        }
+        self.use_emcee = use_emcee
+        self._eep_bounds = eep_bounds
+        self._mass_bounds = mass_bounds
+        self.minq = float(minq)
+        self.name = name
+        self.chunk_rows = chunk_rows
+        self._samples = None
+        self._nested = None
+        self._sampler = None
+        self._fit_kind = None
+        self._dev = {}
+        self._kernel_events = None
+
+    # -- the reference's surface ------------------------------------------------------------
+    @property
+    def ic(self):
+        return self._ic
+
+    @property
+    def bands(self):
+        return tuple(self.stars.bands)
+
+    @property
+    def props(self):
+        return tuple(self.stars.props)
+
+    @property
+    def labelstring(self):
+        return "cluster" + ("_{}".format(self.name) if self.name else "")
+
+    @property
+    def n_params(self):
+        return len(self.param_names)
+
+    def bounds(self, prop):
+        """reference: cluster.py:237-260, with the fall-backs its ``AttributeError`` branch meant: the ic's feh range and
+        (0, 1) for gamma / fB whenever a prior's bounds are missing or not finite."""
+        if prop == "eep":
+            return tuple(self._eep_bounds) if self._eep_bounds is not None else (self.ic.mineep, self.ic.maxeep)
+        if prop == "mass":
+            return tuple(self._mass_bounds) if self._mass_bounds is not None else (self.ic.minmass, self.ic.maxmass)
+        b = getattr(self._priors[prop], "bounds", None)
+        if b is not None and len(b) == 2 and np.all(np.isfinite(np.asarray(b, dtype=float))):
+            return (float(b[0]), float(b[1]))
+        fallback = {"age": (self.ic.minage, self.ic.maxage), "feh": (self.ic.minfeh, self.ic.maxfeh), "gamma": (0.0, 1.0),
+                    "fB": (0.0, 1.0)}
+        if prop in fallback:
+            return tuple(float(v) for v in fallback[prop])
+        return b
+
+    def set_prior(self, **kwargs):
+        """Replace the priors of any of the seven parameters by ``Prior`` objects (or anything with ``lnpdf``)."""
+        for name, pr in kwargs.items():
+            if name not in self.param_names:
+                raise ValueError("no parameter %r (have %s)" % (name, ", ".join(self.param_names)))
+            if not hasattr(pr, "lnpdf"):
+                raise TypeError("the prior of %r has no lnpdf" % name)
+        self._priors.update(kwargs)
+
+    def mnest_prior(self, cube, ndim=None, nparams=None):
+        """Unit cube -> the flat box of ``bounds()``, in place (reference: cluster.py:384-388)."""
+        for i, par in enumerate(self.param_names):
+            lo, hi = self.bounds(par)
+            cube[i] = (hi - lo) * cube[i] + lo
+
+    def emcee_p0(self, n_walkers):
+        raise NotImplementedError("Must provide p0 to fit_mcmc for now.")
+
+    # -- evaluation -------------------------------------------------------------------------
+    def _lnprior_np(self, x):
+        """Sum of the seven priors' lnpdf, in the reference's order (cluster.py:265-287); -inf when not finite."""
+        lnp = np.zeros(x.shape[0])
+        for i, name in enumerate(self.param_names):
+            lnp = lnp + _lnpdf_vec(self._priors[name], x[:, i])
+        return np.where(np.isfinite(lnp), lnp, -np.inf)
+
+    def _device_state(self, device):
+        st = self._dev.get(device)
+        if st is None:
+            import torch
+            vals = [self.stars.measurements[b] for b in self.bands] + [self.stars.measurements[q] for q in self.props]
+            v = np.array([a for a, _ in vals], dtype=float)
+            w = np.array([1.0 / (u * u) for _, u in vals], dtype=float)
+            lo, hi = self.bounds("eep")
+            eeps = np.arange(lo, hi + 1).astype(float)
+            if eeps.size == 0:
+                raise ValueError("empty EEP range %s" % ((lo, hi),))
+            ci = self.ic.model_grid.interp.column_index
+            icols = np.array([ci["initial_mass"], ci["dm_deep"]] + [ci[q] for q in self.props if q != "parallax"],
+                             dtype=np.int32)
+            kw = dict(dtype=torch.float64, device=torch.device("cuda", device))
+            st = dict(val=torch.as_tensor(v, **kw).contiguous(), w=torch.as_tensor(w, **kw).contiguous(),
+                      eeps=torch.as_tensor(eeps, **kw), icols=icols)
+            self._dev[device] = st
+        return st
+
+    def _rows_per_chunk(self, n_eep):
+        if self.chunk_rows:
+            return max(1, int(self.chunk_rows))
+        nb, npr, ns = len(self.bands), len(self.props), len(self.stars)
+        per_row = 8 * n_eep * (ns + 2 * (3 + 2 * nb + npr) + 2 * nb + 16)
+        return max(1, DEFAULT_CHUNK_BYTES // per_row)
+
+    def lnlike_device(self, pars, star_terms=False):
+        """lnlike of the rows of a CUDA float64 tensor ``[P, 7]`` -> CUDA tensor ``[P]`` (and ``ln like_s`` ``[P, N_s]``
+        with ``star_terms``)."""
+        import torch
+        from . import _cluster_cabi as CC
+        device = pars.device.index
+        pars = pars.to(torch.float64).contiguous()
+        st = self._device_state(device)
+        E = st["eeps"]
+        ne = E.numel()
+        ns, nb, npr = len(self.stars), len(self.bands), len(self.props)
+        ncol = 3 + 2 * nb + npr
+        mass_lo, mass_hi = (float(v) for v in self.bounds("mass"))
+        n = pars.shape[0]
+        out = torch.empty(n, dtype=torch.float64, device=pars.device)
+        per_star = torch.empty((n, ns), dtype=torch.float64, device=pars.device) if star_terms else None
+        interp = self.ic.model_grid.interp
+        lib = CC.lib()
+        chunk = self._rows_per_chunk(ne)
+        for c0 in range(0, n, chunk):
+            x = pars[c0:c0 + chunk]
+            p = x.shape[0]
+            age = x[:, 0:1].expand(p, ne).reshape(-1).contiguous()
+            feh = x[:, 1:2].expand(p, ne).reshape(-1).contiguous()
+            eep = E.repeat(p).contiguous()
+            # the interpolation library switches to packed-table kernels (other rounding) for calls of 1 024 points or
+            # more; slices below that keep every point on the same kernel, so a row's columns - and its lnlike - are
+            # bit-identical however the rows are batched
+            pts = p * ne
+            sl = [(a, min(a + INTERP_SLICE, pts)) for a in range(0, pts, INTERP_SLICE)]
+            vals = torch.cat([interp.interp_device([age[a:b], feh[a:b], eep[a:b]], st["icols"], device)
+                              for a, b in sl])                                          # [p*ne, 2 + props]
+            dist = x[:, 2:3].expand(p, ne).reshape(-1)
+            AV = x[:, 3:4].expand(p, ne).reshape(-1)
+            five = torch.stack([eep, age, feh, dist, AV])
+            mags = torch.cat([self.ic.interp_mag_device(five[:, a:b].contiguous(), list(self.bands), device)[3]
+                              for a, b in sl])                                          # [p*ne, nb]
+            mass = vals[:, 0].view(p, ne)
+            valid = torch.isfinite(mass)
+            order = torch.sort((~valid).to(torch.int8), dim=1, stable=True).indices     # kept EEPs first, in order
+            n_valid = valid.sum(dim=1).to(torch.int32).contiguous()
+            take = lambda t: torch.gather(t, 1, order)                                   # noqa: E731
+            alpha, gamma, fB = x[:, 4:5], x[:, 5:6], x[:, 6:7]
+            a1 = alpha + 1.0
+            m_c = take(mass)
+            mass_term = ((torch.log(a1 / (mass_hi ** a1 - mass_lo ** a1)) + alpha * torch.log(m_c))
+                         + torch.log(torch.abs(take(vals[:, 1].view(p, ne)))))
+            mag_c = torch.gather(mags.view(p, ne, nb), 1, order[:, :, None].expand(p, ne, nb)).transpose(1, 2)
+            cols = torch.empty((p, ncol, ne), dtype=torch.float64, device=pars.device)
+            cols[:, 0] = E[order]
+            cols[:, 1] = m_c
+            cols[:, 2] = mass_term
+            cols[:, 3:3 + nb] = torch.pow(10.0, -0.4 * mag_c)
+            cols[:, 3 + nb:3 + 2 * nb] = mag_c
+            k = 2
+            for j, q in enumerate(self.props):
+                if q == "parallax":
+                    cols[:, 3 + 2 * nb + j] = (1000.0 / x[:, 2:3]).expand(p, ne)
+                else:
+                    cols[:, 3 + 2 * nb + j] = take(vals[:, k].view(p, ne))
+                    k += 1
+            g1 = gamma + 1.0
+            rowpar = torch.cat([torch.log(fB), torch.log(1.0 - fB), gamma,
+                                torch.log(g1 / (1.0 - self.minq ** g1))], dim=1).contiguous()
+            work = torch.empty(p * ns * ne, dtype=torch.float64, device=pars.device)
+            o = out[c0:c0 + p]
+            ps = per_star[c0:c0 + p] if star_terms else None
+            if self._kernel_events is not None:                  # (tools/cluster_timing.py: the kernels' own time)
+                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                ev[0].record()
+            CC.check(lib.iso_cluster_lnlike(dev.ptr(cols), ne, p, dev.ptr(n_valid), dev.ptr(rowpar), dev.ptr(st["val"]),
+                                            dev.ptr(st["w"]), ns, nb, npr, self.minq, dev.ptr(work), dev.ptr(o),
+                                            dev.ptr(ps) if ps is not None else None, dev.stream_ptr(device)))
+            if self._kernel_events is not None:
+                ev[1].record()
+                self._kernel_events.append(ev)
+        return (out, per_star) if star_terms else out
+
+    def _evaluate(self, p, which, star_terms=False):
+        import torch
+        is_t = dev.is_tensor(p) and p.is_cuda
+        if is_t:
+            x_t = p.to(torch.float64)
+            single = x_t.dim() == 1
+            x_t = x_t.reshape(-1, self.n_params).contiguous()
+            x = x_t.detach().cpu().numpy()
+        else:
+            x = np.asarray(p, dtype=float)
+            single = x.ndim == 1
+            x = np.ascontiguousarray(x.reshape(-1, self.n_params))
+            x_t = None
+        prior = self._lnprior_np(x)
+        res_star = None
+        if which == "prior":
+            res = prior
+        else:
+            if x_t is None:
+                x_t = torch.as_tensor(x, dtype=torch.float64, device=torch.device("cuda", dev.current_device()))
+            got = self.lnlike_device(x_t, star_terms=star_terms)
+            if star_terms:
+                got, res_star = got
+                res_star = res_star.cpu().numpy()
+            like = got.cpu().numpy()
+            if which == "like":
+                res = like
+            else:
+                with np.errstate(invalid="ignore"):
+                    res = np.where(np.isfinite(prior), prior + like, -np.inf)
+        if is_t:
+            out = torch.as_tensor(res, device=p.device)
+            return out[0] if single else out
+        if single:
+            return (float(res[0]), res_star[0]) if star_terms else float(res[0])
+        return (res, res_star) if star_terms else res
+
+    def lnprior(self, p):
+        return self._evaluate(p, "prior")
+
+    def lnlike(self, p):
+        return self._evaluate(p, "like")
+
+    def lnpost(self, p):
+        """lnprior + lnlike; -inf where the prior is not finite (reference: starmodel.py:538-542)."""
+        return self._evaluate(p, "post")
+
+    def lnlike_stars(self, p):
+        """(lnlike, ln like_s of every member star) of the rows ``p`` (numpy)."""
+        return self._evaluate(p, "like", star_terms=True)
+
+    # -- fits -------------------------------------------------------------------------------
+    def fit_mcmc(self, p0=None, nwalkers=64, nburn=200, niter=200, seed=None, **kwargs):
+        """Affine-invariant ensemble (framework-op :class:`~isochrones_amd.sampler.EnsembleSampler`) started in a small
+        ball around ``p0``, which is required (reference: ``emcee_p0`` raises)."""
+        import torch
+        from .sampler import EnsembleSampler
+        if p0 is None:
+            p0 = self.emcee_p0(nwalkers)
+        rng = np.random.default_rng(seed)
+        centre = np.asarray(p0, dtype=float)
+        if centre.ndim == 1:
+            pos = centre[None, :] + 1e-3 * np.abs(centre)[None, :] * rng.standard_normal((nwalkers, self.n_params)) \
+                + 1e-4 * rng.standard_normal((nwalkers, self.n_params))
+            bad = ~np.isfinite(self.lnpost(pos))
+            pos[bad] = centre
+        else:
+            pos = centre
+        device = torch.device("cuda", dev.current_device())
+        sampler = EnsembleSampler(nwalkers, self.n_params, self.lnpost, seed=int(rng.integers(2 ** 62)), device=device)
+        pos, prob = sampler.run_mcmc(pos, nburn, store=False)
+        sampler.reset()
+        sampler.run_mcmc(pos, niter, lnprob0=prob)
+        self._sampler = sampler
+        self._samples = None
+        self._fit_kind = "mcmc"
+        return sampler
+
+    @property
+    def sampler(self):
+        if self._sampler is None:
+            raise AttributeError("fit_mcmc must be run first")
+        return self._sampler
+
+    @property
+    def samples(self):
+        """DataFrame of the seven parameters and ``lnprob`` (reference: cluster.py:390-412)."""
+        import pandas as pd
+        if self._samples is None:
+            if self._fit_kind == "nested" and self._nested is not None:
+                self._samples = self._nested_frame()
+            elif self._fit_kind == "mcmc":
+                chain = self._sampler.flatchain
+                lnp = self._sampler.flatlnprobability
+                chain = chain.cpu().numpy() if dev.is_tensor(chain) else np.asarray(chain)
+                lnp = lnp.cpu().numpy() if dev.is_tensor(lnp) else np.asarray(lnp)
+                self._samples = pd.DataFrame(chain, columns=list(self.param_names))
+                self._samples["lnprob"] = lnp
+            else:
+                raise AttributeError("no fit has been run")
+        return self._samples
+
+
+def simulate_cluster(N, age, feh, distance, AV, alpha, gamma, fB, bands="JHK", mass_range=(0.8, 2.5),
+                     distance_scatter=5, ic=None, seed=None):
+    """A synthetic cluster catalog (reference: cluster.py:414-477), drawn with ``numpy.random.default_rng(seed)`` and
+    batched ``get_eep`` / ``interp_mag`` calls.  A secondary below the table's mass range has a NaN EEP; a single star's
+    secondary magnitude is infinite, so its total is the primary's."""
+    import pandas as pd
+    from .models import get_ichrone
+    from .utils import addmags
+    rng = np.random.default_rng(seed)
+    bands = list(bands)
+    is_binary = rng.random(N) < fB
+    pri_masses = P.PowerLawPrior(alpha, mass_range).sample(N, rng)
+    qs = P.PowerLawPrior(gamma, (0.1, 1)).sample(N, rng)
+    sec_masses = pri_masses * qs * is_binary
+    if ic is None:
+        ic = get_ichrone("mist", bands=bands)
+    ones = np.ones(N)
+    pri_eeps = np.asarray(ic.get_eep(pri_masses, age * ones, feh * ones), dtype=float).reshape(N)
+    sec_eeps = np.asarray(ic.get_eep(sec_masses, age * ones, feh * ones), dtype=float).reshape(N)
+    distances = distance + rng.standard_normal(N) * distance_scatter
+    _, _, _, mp = ic.interp_mag([pri_eeps, age * ones, feh * ones, distances, AV * ones], bands)
+    _, _, _, ms = ic.interp_mag([sec_eeps, age * ones, feh * ones, distances, AV * ones], bands)
+    mp = np.asarray(mp, dtype=float).reshape(N, len(bands))
+    ms = np.asarray(ms, dtype=float).reshape(N, len(bands)).copy()
+    ms[~is_binary] = np.inf
+    stars = pd.DataFrame({"{}_mag".format(b): addmags(mp[:, i], ms[:, i]) for i, b in enumerate(bands)})
+    stars["is_binary"] = is_binary
+    stars["age"] = age
+    stars["feh"] = feh
+    stars["distance"] = distances
+    stars["AV"] = AV
+    stars["mass_pri"] = pri_masses
+    stars["mass_sec"] = sec_masses
+    stars["eep_pri"] = pri_eeps
+    stars["eep_sec"] = sec_eeps
+    unc = 0.01
+    for b in bands:
+        stars["{}_mag".format(b)] += rng.standard_normal(N) * unc
+        stars["{}_mag_unc".format(b)] = unc
+    stars["parallax"] = 1000.0 / distances
+    stars["parallax_unc"] = 0.2
+    return StarCatalog(stars, bands=bands, props=["parallax"])
