@@ -10,7 +10,8 @@
  *                                       0: EEP, 1: initial mass m_j, 2: powerlaw_lnpdf(m_j; alpha, mass_lo, mass_hi) +
  *                                       ln|dm/dEEP|_j, 3 .. 3+N_b-1: 10^(-0.4 M_jb), 3+N_b .. 3+2N_b-1: M_jb, then the
  *                                       model value of each property
- *   n_valid   [P]      int32            number of valid EEPs of each row (<= ld)
+ *   n_valid   [P]      int32            number of valid EEPs of each row; clamped to [0, ld] (a count below 2 gives
+ *                                       like_s = 0 for every star)
  *   rowpar    [P][4]                    ln fB, ln(1 - fB), gamma, ln C_q (C_q = (gamma+1) / (1 - minq^(gamma+1)))
  *   star_val  [N_b + N_p][N_s]          measured magnitudes, then property values
  *   star_w    [N_b + N_p][N_s]          1 / uncertainty^2 of the same

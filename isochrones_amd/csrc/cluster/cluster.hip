@@ -186,12 +186,10 @@ int iso_cluster_lnlike(const double* cols, int64_t ld, int64_t n_rows, const int
     if (blocks > INT32_MAX || n_rows > INT32_MAX)
         return fail(ISO_CLUSTER_ERR_INVALID, "iso_cluster_lnlike: too many rows in one call (split the batch)");
     const size_t lds = (size_t)(4 * n_bands + 2) * TILE * sizeof(double) + TILE * sizeof(int);
-    static bool big_lds = false;
-    if (lds > 64 * 1024 && !big_lds) {
-        if (hipFuncSetAttribute((const void*)k_cluster_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)
-            return fail(ISO_CLUSTER_ERR_HIP, "iso_cluster_lnlike: hipFuncSetAttribute failed");
-        big_lds = true;
-    }
+    // function attributes are per device: raise the limit before every large launch, on whichever device is current
+    if (lds > 64 * 1024 &&
+        hipFuncSetAttribute((const void*)k_cluster_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)
+        return fail(ISO_CLUSTER_ERR_HIP, "iso_cluster_lnlike: hipFuncSetAttribute failed");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_cluster_pairs, dim3((unsigned)blocks), dim3(TILE), lds, st, cols, ld, tiles, n_valid, rowpar,
                        star_val, star_w, n_stars, n_bands, n_props, minq, work);

@@ -1,12 +1,16 @@
 """StarClusterModel on the device (libiso_cluster.so): the reference's own numbers (tests/golden/cluster/) in every calling
-form, the numpy restatement (tests/_cluster_ref.py) at shapes too large for fixtures, bitwise row independence, and fits."""
+form, the numpy restatement (tests/_cluster_ref.py) at shapes too large for fixtures, the long-double reference
+(tests/_cluster_hp.py) over columns from the CPU oracle at 32 bands, 8 properties and the notebook shape, bitwise row
+independence, and fits."""
 import numpy as np
 import pandas as pd
 import pytest
 
 import isochrones_amd as ia
 
+from . import _cluster_hp as H
 from . import _cluster_ref as R
+from . import _fixtures as fx
 
 pytestmark = pytest.mark.gpu
 
@@ -220,3 +224,73 @@ def test_fit_mcmc_and_fit_dispatch(fit_model):
     nest.fit_multinest = lambda **kw: called.append(kw)
     nest.fit(n_live_points=10)
     assert called == [dict(n_live_points=10)]
+
+
+# -- the public path against columns from the CPU oracle and the long-double reference ---------------------------------
+def _oracle_expected(mod, rows):
+    """(lnlike [P], ln like_s [P][N_s]) without libiso_hip.so: each row's per-EEP columns from the CPU oracle's
+    interpolators, compacted to the EEPs with a finite initial_mass as the model does, then the long-double reference."""
+    ic = mod.ic
+    oic = fx.make_oracle_ic(ic)
+    ci = ic.model_grid.interp.column_index
+    others = [q for q in mod.props if q != "parallax"]
+    icols = [ci["initial_mass"], ci["dm_deep"]] + [ci[q] for q in others]
+    bc = [ic.bc_grid.interp.column_index[b] for b in mod.bands]
+    lo, hi = mod.bounds("eep")
+    E = np.arange(lo, hi + 1).astype(float)
+    mass_lo, mass_hi = mod.bounds("mass")
+    nb, npr = len(mod.bands), len(mod.props)
+    cols, rowpar, n_valid = [], [], []
+    for p in rows:
+        o = np.ones(E.size)
+        v = oic.model.interp([p[0] * o, p[1] * o, E], icols)
+        ok = np.isfinite(v[:, 0])
+        Ek, ko = E[ok], o[ok]
+        _, _, _, mags = oic.interp_mag(np.array([Ek, p[0] * ko, p[1] * ko, p[2] * ko, p[3] * ko]), bc)
+        props = np.column_stack([1000.0 / p[2] * ko if q == "parallax" else v[ok, 2 + others.index(q)]
+                                 for q in mod.props]) if npr else np.zeros((Ek.size, 0))
+        c, rp = H.row_columns(Ek, v[ok, 0], np.log(np.abs(v[ok, 1])), mags, props, p[4], p[5], p[6], mod.minq, mass_lo,
+                              mass_hi, E.size)
+        cols.append(c)
+        rowpar.append(rp)
+        n_valid.append(Ek.size)
+    meas = [mod.stars.measurements[b] for b in mod.bands] + [mod.stars.measurements[q] for q in mod.props]
+    val = np.array([a for a, _ in meas], dtype=float)
+    w = np.array([1.0 / (u * u) for _, u in meas], dtype=float)
+    tot, ln = H.lnlike(np.array(cols), n_valid, np.array(rowpar), val, w, mod.minq, nb, npr)
+    return tot.astype(float), ln.astype(float), np.array(n_valid)
+
+
+def _check_oracle(mod, rows):
+    lnl, per_star = mod.lnlike_stars(np.asarray(rows, dtype=float))
+    tot, ln, n_valid = _oracle_expected(mod, rows)
+    _close(per_star, ln, "ln like_s (oracle columns, long double)")
+    _close(lnl, tot, "lnlike (oracle columns, long double)")
+    return lnl, per_star, n_valid
+
+
+def test_32_bands_and_8_props_against_oracle_columns():
+    bands = tuple(list(ia.grids.KNOWN_BANDS) + ["X%02d" % j for j in range(32)])[:32]
+    others = ("radius", "logTeff", "Teff", "logg", "logL", "Mbol", "density")
+    ic = ia.synthetic_isochrone(bands=bands, ages=np.array([8.5, 9.0, 9.5]), fehs=np.array([-0.5, 0.0, 0.5]),
+                                eeps=np.arange(140.0, 240.0), limits=dict(mass=(0.1, 300.0)))
+    rng = np.random.default_rng(32)
+    df = _stars(ic, rng, 20, 9.0, -0.1, 400.0, 0.1, bands, (180.0, 230.0))
+    e = rng.uniform(180.0, 230.0, len(df))
+    o = np.ones(len(df))
+    truth = np.asarray(ic.interp_value([e, 9.0 * o, -0.1 * o], list(others)), dtype=float).reshape(len(df), len(others))
+    for i, q in enumerate(others):
+        unc = 0.05 * np.abs(truth[:, i]) + 0.05
+        df[q] = truth[:, i] + unc * rng.standard_normal(len(df))
+        df[q + "_unc"] = unc
+    mod = ia.StarClusterModel(ic, df, bands=list(bands), props=["parallax"] + list(others), eep_bounds=(141, 238), minq=0.1)
+    assert len(mod.bands) == 32 and len(mod.props) == 8
+    lnl, per_star, n_valid = _check_oracle(mod, ROWS)
+    assert np.all(n_valid > 64) and np.isfinite(per_star).sum() >= 20
+
+
+def test_notebook_shape_against_oracle_columns(notebook):
+    rows = np.array(TRUTH_NB) + np.array([[0.0] * 7, [0.02, 0.03, 5.0, 0.01, 0.2, 0.05, 0.05],
+                                           [-0.02, -0.03, -5.0, 0.01, -0.2, -0.05, 0.05]])
+    lnl, per_star, n_valid = _check_oracle(notebook, rows)
+    assert np.isfinite(lnl).all() and np.all(n_valid > 256)
