@@ -15,15 +15,27 @@ import os
 import numpy as np
 
 from . import _cabi, device as dev
+from ._handles import Handles, PreparedCalls
 
 
 HOST_CALL_ROWS = 4096     # host inputs up to this many rows use the *_host entry points (one launch + one sync)
-TABLE_EPOCH = [0]         # bumped whenever ANY interpolator frees its device tables (release / add_column): per-call caches
-                          # that skip ic.handle() (StarModel._scalar_call, the mailbox accessors) compare this integer
+TABLE_EPOCH = [0]         # bumped whenever ANY interpolator frees its device tables (release / add_column): prepared calls
+                          # that skip ic.handle() (the star models' _DeviceModelMixin._scalar_call) compare this integer
 
 
 def _is_scalar(v):
     return isinstance(v, (float, int)) and not isinstance(v, bool)
+
+
+class _ScalarInterp:
+    """``iso_interp_host`` of one point: a coordinate buffer, the column numbers, an output buffer and the call's
+    arguments (table handle and addresses)."""
+    __slots__ = ("fn", "args", "x", "cols", "out")
+
+    def __init__(self, handle, ndim, icols):
+        self.x, self.cols, self.out = (C.c_double * ndim)(), icols, np.empty(icols.size)
+        self.fn = _cabi.lib().iso_interp_host
+        self.args = (handle, C.addressof(self.x), 1, icols.ctypes.data, icols.size, self.out.ctypes.data)
 
 
 class DFInterpolator:
@@ -35,9 +47,9 @@ class DFInterpolator:
         # it is (iso_table_create_from_device) and the host copy behind `grid` is only made if somebody asks for it
         self._device_grid = device_grid
         self._grid = None
-        self._handles = {}          # device index -> iso_table*
-        self._generation = 0        # bumped whenever device tables are freed: dependants compare generations, not
-                                    # pointer values (a new table often lands on the address of the freed one)
+        self._handles = Handles("iso_table_destroy")         # device index -> iso_table*; what is built on a table compares
+                                                             # self._handles.generation
+        self._scalar_calls = PreparedCalls()
         if df is not None:
             self.columns = list(df.columns)
             self.index_columns = tuple(np.array(l, dtype=float) for l in df.index.levels)
@@ -127,30 +139,27 @@ class DFInterpolator:
         """iso_table* for `device` (uploaded once, then resident in HBM)."""
         if device is None:
             device = dev.current_device()
-        h = self._handles.get(device)
-        if h is None:
-            ctx = dev.context(device)
-            shape = (C.c_int64 * (self.ndim + 1))(*self.grid_shape)
-            dp = C.POINTER(C.c_double)
-            axes = (dp * self.ndim)(*[a.ctypes.data_as(dp) for a in self.index_columns])
-            h = C.c_void_p()
-            dg = self._device_grid
-            if dg is not None and dg.device.index == device and hasattr(_cabi.lib(), "iso_table_create_from_device"):
-                # the values are on this device already: one device-to-device copy instead of a download and an upload
-                _cabi.check(_cabi.lib().iso_table_create_from_device(ctx, self.ndim, shape, dev.ptr(dg), axes, C.byref(h)))
-                if self._grid is not None:
-                    self._device_grid = None            # (a host copy exists: the tensor is not needed any more)
-            else:
-                _cabi.check(_cabi.lib().iso_table_create(ctx, self.ndim, shape, self.grid.ctypes.data_as(dp),
-                                                         axes, C.byref(h)))
-            self._handles[device] = h
+        return self._handles.get(device, None, lambda: self._create(device))
+
+    def _create(self, device):
+        ctx = dev.context(device)
+        shape = (C.c_int64 * (self.ndim + 1))(*self.grid_shape)
+        dp = C.POINTER(C.c_double)
+        axes = (dp * self.ndim)(*[a.ctypes.data_as(dp) for a in self.index_columns])
+        h = C.c_void_p()
+        dg = self._device_grid
+        if dg is not None and dg.device.index == device and hasattr(_cabi.lib(), "iso_table_create_from_device"):
+            # the values are on this device already: one device-to-device copy instead of a download and an upload
+            _cabi.check(_cabi.lib().iso_table_create_from_device(ctx, self.ndim, shape, dev.ptr(dg), axes, C.byref(h)))
+            if self._grid is not None:
+                self._device_grid = None            # (a host copy exists: the tensor is not needed any more)
+        else:
+            _cabi.check(_cabi.lib().iso_table_create(ctx, self.ndim, shape, self.grid.ctypes.data_as(dp),
+                                                     axes, C.byref(h)))
         return h
 
     def release(self):
-        for h in self._handles.values():
-            _cabi.lib().iso_table_destroy(h)
-        self._handles = {}
-        self._generation += 1
+        self._handles.release()
         TABLE_EPOCH[0] += 1
 
     def __del__(self):
@@ -193,32 +202,24 @@ class DFInterpolator:
         """One point given as plain numbers (the call form of the reference's notebooks and of optimisers that walk the
         table, interp.py:631-660): everything a call needs besides the numbers - the table handle, the column numbers, a
         coordinate buffer, an output buffer and their addresses - is kept per thread and per column list and revalidated by
-        one integer comparison, so that the wrapper adds about a microsecond to the C call (which the context's resident
-        service wave answers without a launch)."""
-        tls = self.__dict__.get("_scalar_tls")
-        if tls is None:
-            import threading
-            tls = self.__dict__.setdefault("_scalar_tls", threading.local())
-        cache = tls.__dict__.get("c")
-        if cache is None or cache[0] != self._generation:
-            cache = tls.c = (self._generation, {})
-        key = cols if type(cols) is str else tuple(cols)
-        c = cache[1].get(key)
+        one integer comparison (_handles.PreparedCalls), so that the wrapper adds about a microsecond to the C call (which
+        the context's resident service wave answers without a launch)."""
+        c = self._scalar_calls.get(cols if type(cols) is str else tuple(cols), self._handles.generation, self._prepare_scalar)
         if c is None:
-            icols = self._icols(cols)
-            if icols.size == 0 or icols.size > _cabi.ISO_MAX_COLS:
-                return None
-            xbuf = (C.c_double * self.ndim)()
-            out = np.empty(icols.size)
-            c = cache[1][key] = (self.handle(dev.current_device()), xbuf, C.addressof(xbuf), icols, icols.ctypes.data, icols.size, out,
-                                 out.ctypes.data, _cabi.lib().iso_interp_host)
-        xbuf = c[1]
+            return None
+        x = c.x
         for d in range(self.ndim):
-            xbuf[d] = p[d]
-        rc = c[8](c[0], c[2], 1, c[4], c[5], c[7])
+            x[d] = p[d]
+        rc = c.fn(*c.args)
         if rc:
             _cabi.check(rc)
-        return c[6].copy()
+        return c.out.copy()
+
+    def _prepare_scalar(self, cols):
+        icols = self._icols(cols)
+        if icols.size == 0 or icols.size > _cabi.ISO_MAX_COLS:
+            return None
+        return _ScalarInterp(self.handle(dev.current_device()), self.ndim, icols)
 
     def __call__(self, p, cols="all"):
         tp = type(p)

@@ -16,10 +16,8 @@ import ctypes as C
 import numpy as np
 
 from . import _cabi, device as dev, grids
-from .interp import DFInterpolator
-
-
-from .interp import HOST_CALL_ROWS
+from ._handles import Handles, PreparedCalls
+from .interp import HOST_CALL_ROWS, DFInterpolator
 
 
 class TableGrid:
@@ -78,6 +76,30 @@ class BolometricCorrectionGrid(TableGrid):
     """index (Teff, logg, [Fe/H], Av), one column per band — reference: isochrones/bc.py:9-118"""
 
 
+class _ScalarMag:
+    """``iso_interp_mag_host`` of one point: one buffer [pars | Teff logg feh | mags], the band columns and the call's
+    arguments (handle and addresses)."""
+    __slots__ = ("fn", "args", "buf", "bands")
+
+    def __init__(self, handle, band_cols):
+        self.bands, bands_ptr = dev.i32_array(band_cols)
+        self.buf = np.empty(8 + len(band_cols))
+        self.fn = _cabi.lib().iso_interp_mag_host
+        a = self.buf.ctypes.data
+        self.args = (handle, a, 1, bands_ptr, len(band_cols), a + 40, a + 48, a + 56, a + 64)
+
+
+class _ScalarEEP:
+    """``iso_interp_eep_host`` of one point: one buffer [age feh mass | eep] and the call's arguments."""
+    __slots__ = ("fn", "args", "buf")
+
+    def __init__(self, handle):
+        self.buf = (C.c_double * 4)()
+        self.fn = _cabi.lib().iso_interp_eep_host
+        a = C.addressof(self.buf)
+        self.args = (handle, a, a + 8, a + 16, 1, a + 24)          # table, age, feh, mass, one point, eep
+
+
 class ModelGridInterpolator:
     param_names = None
     eep_replaces = None
@@ -92,9 +114,9 @@ class ModelGridInterpolator:
         self.param_index_order = list(self._param_index_order)
         if eep_bounds is not None:
             self.eep_bounds = tuple(eep_bounds)
-        self._handles = {}
-        self._handle_tables = {}
-        self._generation = 0        # bumped whenever an iso_ic is destroyed (models bound to it rebuild)
+        self._handles = Handles("iso_ic_destroy")       # device -> iso_ic*; models built on one compare its generation
+        self._eep_handles = Handles("iso_eep_table_destroy")
+        self._mag_calls, self._eep_calls = PreparedCalls(), PreparedCalls()
         ci = model_grid.interp.column_index
         missing = [c for c in ("Teff", "logg", "feh", "Mbol") if c not in ci]
         if missing:
@@ -152,32 +174,21 @@ class ModelGridInterpolator:
             device = dev.current_device()
         mg = self.model_grid.interp.handle(device)
         bc = self.bc_grid.interp.handle(device)
-        h = self._handles.get(device)
-        tables = (self.model_grid.interp._generation, self.bc_grid.interp._generation)
-        if h is not None and self._handle_tables.get(device) != tables:
-            _cabi.lib().iso_ic_destroy(h)      # a table was rebuilt (add_column): rebind
-            self._generation += 1
-            h = None
-        if h is None:
-            ctx = dev.context(device)
-            keep0, cols = dev.i32_array(self._cols)          # keep the arrays alive across the call
-            keep1, pcols = dev.i32_array(self._prior_cols)
-            keep2, acols = dev.i32_array(self._astero_cols)
-            h = C.c_void_p()
-            _cabi.check(_cabi.lib().iso_ic_create(ctx, mg, bc, self.kind, cols, pcols, acols, C.byref(h)))
-            self._handles[device] = h
-            self._handle_tables[device] = tables
+        # a table rebuilt (add_column) has a new generation: the iso_ic is rebound to it
+        return self._handles.get(device, (self.model_grid.interp._handles.generation, self.bc_grid.interp._handles.generation),
+                             lambda: self._create(device, mg, bc))
+
+    def _create(self, device, mg, bc):
+        keep0, cols = dev.i32_array(self._cols)          # keep the arrays alive across the call
+        keep1, pcols = dev.i32_array(self._prior_cols)
+        keep2, acols = dev.i32_array(self._astero_cols)
+        h = C.c_void_p()
+        _cabi.check(_cabi.lib().iso_ic_create(dev.context(device), mg, bc, self.kind, cols, pcols, acols, C.byref(h)))
         return h
 
     def release(self):
-        for h in self._handles.values():
-            _cabi.lib().iso_ic_destroy(h)
-        self._handles = {}
-        self._handle_tables = {}
-        self._generation = getattr(self, "_generation", 0) + 1
-        for h in getattr(self, "_eep_handles", {}).values():
-            _cabi.lib().iso_eep_table_destroy(h)
-        self._eep_handles = {}
+        self._handles.release()
+        self._eep_handles.release()
 
     def __del__(self):
         try:
@@ -246,40 +257,26 @@ class ModelGridInterpolator:
     def _scalar_interp_mag(self, pars, bands):
         """interp_mag of five plain numbers (the reference's scalar form, models.py:416-431): handle, band columns, one
         buffer [pars | Teff logg feh | mags] and its addresses are kept per thread and band list (revalidated by the
-        interpolator's generation number); the C call is answered by the context's resident service wave."""
+        generations of the handles it was built on); the C call is answered by the context's resident service wave."""
         for x in pars:
             if not isinstance(x, (float, int, np.floating, np.integer)) or isinstance(x, bool):
                 return None
-        tls = self.__dict__.get("_scalar_tls")
-        if tls is None:
-            import threading
-            tls = self.__dict__.setdefault("_scalar_tls", threading.local())
-        cache = tls.__dict__.get("c")
-        gen = (self._generation, self.model_grid.interp._generation, self.bc_grid.interp._generation)
-        if cache is None or cache[0] != gen:
-            cache = tls.c = (gen, {})
-        key = tuple(bands) if bands else ()
-        c = cache[1].get(key)
+        valid = (self._handles.generation, self.model_grid.interp._handles.generation, self.bc_grid.interp._handles.generation)
+        c = self._mag_calls.get(tuple(bands) if bands else (), valid, self._prepare_mag)
         if c is None:
-            nb = len(key)
-            if nb > _cabi.ISO_MAX_BANDS:
-                return None
-            h = self.handle(dev.current_device())
-            gen = (self._generation, self.model_grid.interp._generation, self.bc_grid.interp._generation)
-            if cache[0] != gen:                      # (handle() rebound the interpolator)
-                cache = tls.c = (gen, {})
-            buf = np.empty(8 + nb)
-            base = buf.ctypes.data
-            keep, bcp = dev.i32_array(self._band_cols(list(key)))
-            c = cache[1][key] = (h, buf, base, keep, bcp, nb, _cabi.lib().iso_interp_mag_host)
-        buf = c[1]
+            return None
+        buf = c.buf
         buf[0], buf[1], buf[2], buf[3], buf[4] = pars
-        base = c[2]
-        rc = c[6](c[0], base, 1, c[4], c[5], base + 40, base + 48, base + 56, base + 64)
+        rc = c.fn(*c.args)
         if rc:
             _cabi.check(rc)
         out = buf[5:].copy()
         return out[0], out[1], out[2], out[3:]
+
+    def _prepare_mag(self, bands):
+        if len(bands) > _cabi.ISO_MAX_BANDS:
+            return None
+        return _ScalarMag(self.handle(dev.current_device()), self._band_cols(list(bands)))
 
     def interp_mag(self, pars, bands):
         """(Teff, logg, feh, mags) at ``pars`` = the five ``param_names``.
@@ -366,21 +363,19 @@ class ModelGridInterpolator:
     def _eep_handle(self, device):
         if self.eep_replaces != "age":
             raise NotImplementedError("get_eep needs the evolution-track parametrisation (as the reference)")
-        h = getattr(self, "_eep_handles", {}).get(device)
-        if h is None:
-            from .ingest import ragged_age_arrays
-            dfi = self.model_grid.interp
-            ages, lengths = ragged_age_arrays(dfi, "age")
-            self._age_grid, self._array_lengths = ages, lengths
-            dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int64)
-            fehs, masses, eeps = dfi.index_columns
-            h = C.c_void_p()
-            _cabi.check(_cabi.lib().iso_eep_table_create(
-                dev.context(device), ages.ctypes.data_as(dp), lengths.ctypes.data_as(ip), fehs.ctypes.data_as(dp),
-                fehs.size, masses.ctypes.data_as(dp), masses.size, ages.shape[1], float(eeps[0]), C.byref(h)))
-            if not hasattr(self, "_eep_handles"):
-                self._eep_handles = {}
-            self._eep_handles[device] = h
+        return self._eep_handles.get(device, None, lambda: self._create_eep(device))
+
+    def _create_eep(self, device):
+        from .ingest import ragged_age_arrays
+        dfi = self.model_grid.interp
+        ages, lengths = ragged_age_arrays(dfi, "age")
+        self._age_grid, self._array_lengths = ages, lengths
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+        fehs, masses, eeps = dfi.index_columns
+        h = C.c_void_p()
+        _cabi.check(_cabi.lib().iso_eep_table_create(
+            dev.context(device), ages.ctypes.data_as(dp), lengths.ctypes.data_as(ip), fehs.ctypes.data_as(dp),
+            fehs.size, masses.ctypes.data_as(dp), masses.size, ages.shape[1], float(eeps[0]), C.byref(h)))
         return h
 
     def max_eep(self, mass, feh):
@@ -438,20 +433,11 @@ class ModelGridInterpolator:
         if type(mass) in (float, int, np.float64) and type(age) in (float, int, np.float64) and type(feh) in (float, int, np.float64):
             # the call form of the reference's notebooks: three plain numbers, one C call (the context's resident service
             # wave); buffers and the table handle kept per thread
-            tls = self.__dict__.get("_eep_tls")
-            if tls is None:
-                import threading
-                tls = self.__dict__.setdefault("_eep_tls", threading.local())
-            c = tls.__dict__.get("c")
-            if c is None or c[0] != self._generation or c[1] != self.model_grid.interp._generation:
-                h = self._eep_handle(dev.current_device())
-                buf = (C.c_double * 4)()
-                base = C.addressof(buf)
-                c = tls.c = (self._generation, self.model_grid.interp._generation, h, buf, base, _cabi.lib().iso_interp_eep_host)
-            buf = c[3]
+            c = self._eep_calls.get(None, self._eep_handles.generation,
+                                    lambda _: _ScalarEEP(self._eep_handle(dev.current_device())))
+            buf = c.buf
             buf[0], buf[1], buf[2] = age, feh, mass
-            base = c[4]
-            rc = c[5](c[2], base, base + 8, base + 16, 1, base + 24)
+            rc = c.fn(*c.args)
             if rc:
                 _cabi.check(rc)
             return buf[3]

@@ -37,8 +37,8 @@ def _ncdf(z):
     return 0.5 * math.erfc(-z / math.sqrt(2.0))
 
 
-#: bumped whenever ANY prior object (or a model's EEP prior) is mutated: a model's cached scalar-call state
-#: (starmodel.BasicStarModel._scalar_call) is valid as long as this number has not moved
+#: bumped whenever ANY prior object (or a model's EEP prior) is mutated: a star model's prepared one-row call
+#: (starmodel._DeviceModelMixin._scalar_call) is valid as long as this number has not moved
 EPOCH = [0]
 
 

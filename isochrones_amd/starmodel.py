@@ -17,11 +17,12 @@ from __future__ import annotations
 import ctypes as C
 import logging
 import math
-import threading
 
 import numpy as np
 
-from . import _cabi, device as dev
+from . import _cabi, device as dev, priors as _p
+from ._handles import Handles, PreparedCalls
+from .interp import TABLE_EPOCH
 from .priors import (AgePrior, AVPrior, ChabrierPrior, DistancePrior, FehPrior, DEVICE_PRIOR_TYPES, check_host_prior,
                      flat_stand_in, is_host_prior, lnpdf_array)
 
@@ -60,7 +61,6 @@ class EEPPrior:
 
     @bounds.setter
     def bounds(self, new):
-        from . import priors as _p
         self._bounds = tuple(new)
         _p.EPOCH[0] += 1
 
@@ -75,7 +75,6 @@ class EEPPrior:
         if not isinstance(prior, DEVICE_PRIOR_TYPES):
             raise NotImplementedError("prior %r is not evaluable on the device" % (prior,))
         self._orig_prior = prior
-        from . import priors as _p
         _p.EPOCH[0] += 1
         for owner in list(self._owners):
             owner._dirty()
@@ -137,6 +136,162 @@ class _HostPriorMixin:
         hp = torch.as_tensor(self._host_lnprior(terms, pars.detach().cpu().numpy()), device=pars.device)
         fin = torch.isfinite(hp)
         return tuple(None if o is None else torch.where(fin, o + hp, hp) for o in outs)
+
+
+class _ScalarRow:
+    """lnpost / lnprior / lnlike of one host row: a row buffer, an output buffer [lnpost lnprior lnlike], the call's
+    arguments for each ``which`` (handle, addresses) and the host-prior terms with the bounds they were built for."""
+    __slots__ = ("fn", "args", "row", "out", "terms", "bounds")
+
+    def __init__(self, fn, handle, n_params, terms):
+        self.fn, self.terms, self.bounds = fn, terms, _host_bounds(terms)
+        self.row, self.out = np.empty(n_params), np.zeros(3)
+        h, r, (a, b, c) = handle, self.row.ctypes.data, (self.out.ctypes.data + 8 * k for k in range(3))
+        self.args = {None: (h, r, 1, a, b, c), 0: (h, r, 1, a, None, None), 1: (h, r, 1, None, b, None),
+                     2: (h, r, 1, None, None, c)}
+
+
+def _host_bounds(terms):
+    return tuple([tuple(pr.bounds) for _, pr, _ in terms])
+
+
+class _DeviceModelMixin(_HostPriorMixin):
+    """The device side of BasicStarModel and TreeStarModel: the model handle, per device and rebuilt when the
+    interpolator or any prior object it was packed from has changed, and lnpost / lnprior / lnlike of one row, numpy
+    rows and CUDA rows.  A class names its C entry points (``_c_create``, ``_c_destroy``, ``_c_lnpost``,
+    ``_c_lnpost_host``), its descriptor (``_desc``) and the most rows its host-array path takes (``_host_rows``)."""
+
+    _host_rows = math.inf
+
+    def _init_device(self):
+        self._handles = Handles(self._c_destroy)
+        self._scalar_calls = PreparedCalls()
+
+    def _dirty(self):
+        self._handles.release()
+
+    def handle(self, device=None):
+        if device is None:
+            device = dev.current_device()
+        ich = self.ic.handle(device)
+        return self._handles.get(device, (self.ic._handles.generation, _prior_state(self._priors)),
+                                 lambda: self._create(ich))
+
+    def _create(self, ich):
+        desc = self._desc()
+        h = C.c_void_p()
+        _cabi.check(getattr(_cabi.lib(), self._c_create)(ich, C.byref(desc), C.byref(h)))
+        return h
+
+    def __del__(self):
+        try:
+            self._dirty()
+        except Exception:
+            pass
+
+    def _evaluate_device(self, pars, soa, parts):
+        """pars: CUDA float64 tensor, [N, n_params] (or [n_params, N] if soa).  Returns lnpost[N] or (lnpost, lnprior,
+        lnlike)."""
+        if pars.dim() != 2 or pars.dtype.itemsize != 8 or not pars.dtype.is_floating_point:
+            raise ValueError("pars must be a 2-D float64 tensor")
+        npar = self.n_params
+        if soa:
+            if pars.shape[0] != npar:
+                raise ValueError("expected [%d, N]" % npar)
+            n, stride_n, stride_p = pars.shape[1], 1, pars.shape[1]
+        else:
+            if pars.shape[1] != npar:
+                raise ValueError("expected [N, %d]" % npar)
+            n, stride_n, stride_p = pars.shape[0], npar, 1
+        device = pars.device.index
+        pars = pars.contiguous()
+        post = dev.empty_f64((n,), device)
+        prior = dev.empty_f64((n,), device) if parts else None
+        like = dev.empty_f64((n,), device) if parts else None
+        if n:
+            _cabi.check(getattr(_cabi.lib(), self._c_lnpost)(self.handle(device), dev.ptr(pars), stride_n, stride_p, n,
+                                                             dev.ptr(post), dev.ptr(prior), dev.ptr(like),
+                                                             dev.stream_ptr(device)))
+            terms = self._host_terms()
+            if terms:
+                post, prior = self._host_adjust_tensors(terms, pars.t() if soa else pars, (post, prior))
+        return (post, prior, like) if parts else post
+
+    def evaluate_device(self, pars, parts=False):
+        """pars: CUDA float64 [N, n_params] -> lnpost [N] or (lnpost, lnprior, lnlike)."""
+        return self._evaluate_device(pars, False, parts)
+
+    def _prepare_scalar(self, _key):
+        return _ScalarRow(getattr(_cabi.lib(), self._c_lnpost_host), self.handle(dev.current_device()), self.n_params,
+                          self._host_terms())
+
+    def _scalar_call(self, p, which):
+        """lnpost / lnprior / lnlike of ONE host row as a float, or all three for ``which=None``: the per-point callback
+        of emcee / MultiNest (reference starmodel.py:538-542, 797, 952, 966).  Everything a call needs besides the
+        numbers is prepared once per thread (_ScalarRow) and revalidated by comparing four integers - no prior object
+        anywhere was mutated, the interpolator was not rebound, no table was freed, this model's handle was not
+        destroyed - and, for a model with host priors, their bounds (a foreign prior object's bounds move no counter).
+        The wrapper adds about a microsecond to the C call, which the model's resident mailbox wave answers without a
+        launch."""
+        valid = (_p.EPOCH[0], self._ic._handles.generation, TABLE_EPOCH[0], self._handles.generation)
+        c = self._scalar_calls.get(None, valid, self._prepare_scalar)
+        if c.terms and c.bounds != _host_bounds(c.terms):
+            self._scalar_calls.clear()
+            c = self._scalar_calls.get(None, valid, self._prepare_scalar)
+        c.row[:] = p                                     # (a row of the wrong length raises here)
+        rc = c.fn(*c.args[which])
+        if rc:
+            _cabi.check(rc)
+        out = c.out
+        if c.terms and which != 2:                       # priors evaluated on the host (_HostPriorMixin): add them
+            out = self._host_combine(out[:2], self._host_lnprior(c.terms, c.row[None, :]))
+        if which is None:
+            return float(out[0]), float(out[1]), float(c.out[2])
+        return float(out[which])
+
+    def _evaluate(self, p, which, soa=False):
+        tp = type(p)
+        if ((tp is list or tp is tuple or (tp is np.ndarray and p.ndim == 1)) and len(p) == self.n_params
+                and not isinstance(p[0], (list, tuple, np.ndarray))):     # (a list of n_params ROWS is a batch)
+            return self._scalar_call(p, which)
+        if dev.is_tensor(p) and p.is_cuda:
+            single = p.dim() == 1
+            out = self._evaluate_device(p.double()[None, :] if single else p.double(), soa and not single, which != 0)
+            out = out if which == 0 else out[which]
+            return out[0] if single else out
+        arr = np.ascontiguousarray(p, dtype=np.float64)
+        single = arr.ndim == 1
+        a2 = arr[None, :] if single else arr
+        device = dev.current_device()
+        if (single or not soa) and a2.ndim == 2 and a2.shape[0] <= self._host_rows:
+            # host arrays: one C call.  Sampler-callback sizes go through a pinned staging buffer (one launch, completion
+            # flag); a Basic model's large batches through the chunked upload / download pipeline of iso_lnpost_host
+            if a2.shape[1] != self.n_params:
+                raise ValueError("expected [N, %d]" % self.n_params)
+            n = a2.shape[0]
+            out = np.empty(n)
+            ptrs = [None, None, None]
+            ptrs[which] = out.ctypes.data
+            rc = getattr(_cabi.lib(), self._c_lnpost_host)(self.handle(device), a2.ctypes.data, n, *ptrs)
+            if rc:
+                _cabi.check(rc)
+            if which != 2:
+                terms = self._host_terms()
+                if terms:
+                    out = self._host_combine(out, self._host_lnprior(terms, a2))
+            return float(out[0]) if single else out
+        out = self._evaluate_device(dev.to_device_f64(a2, device), soa and not single, which != 0)
+        out = (out if which == 0 else out[which]).cpu().numpy()
+        return float(out[0]) if single else out
+
+    def lnpost(self, p):
+        return self._evaluate(p, 0)
+
+    def lnprior(self, p):
+        return self._evaluate(p, 1)
+
+    def lnlike(self, p):
+        return self._evaluate(p, 2)
 
 
 class _ConvenienceMixin:
@@ -349,9 +504,10 @@ class _NestedFitMixin:
         return df
 
 
-class BasicStarModel(_NestedFitMixin, _ConvenienceMixin, _HostPriorMixin):
+class BasicStarModel(_NestedFitMixin, _ConvenienceMixin, _DeviceModelMixin):
     def __init__(self, ic, eep_bounds=None, name="", directory=".", N=1, maxAV=None, max_distance=None,
                  halo_fraction=None, ra=None, dec=None, obs=None, use_emcee=False, **kwargs):
+        self._init_device()
         self._ic = ic
         self.eep_bounds = tuple(eep_bounds) if eep_bounds is not None else tuple(ic.eep_bounds)
         self.name = str(name)
@@ -398,7 +554,6 @@ class BasicStarModel(_NestedFitMixin, _ConvenienceMixin, _HostPriorMixin):
                 self.set_bounds(distance=(0, 1.0 / np.abs(unc) * 2000))
         if halo_fraction is not None:
             self._priors["feh"] = FehPrior(halo_fraction=halo_fraction)
-        self._handles, self._handle_ic, self._handle_state = {}, {}, {}
 
     # -- star.ini files (reference: StarModel.from_ini, starmodel.py:248-436; write_ini, 1485-1499) ------
     @staticmethod
@@ -571,156 +726,24 @@ class BasicStarModel(_NestedFitMixin, _ConvenienceMixin, _HostPriorMixin):
             d.bound_lo[j], d.bound_hi[j] = self.bounds(par)
         return d
 
-    # -- device -----------------------------------------------------------------------------
-    def _dirty(self):
-        for h in getattr(self, "_handles", {}).values():
-            _cabi.lib().iso_model_destroy(h)
-        self._handles = {}
-        self._handle_ic = {}
-        self._handle_state = {}
-        self._scalar_cache = None
+    # -- device (_DeviceModelMixin) ------------------------------------------------------------
+    _c_create, _c_destroy, _c_lnpost, _c_lnpost_host = "iso_model_create", "iso_model_destroy", "iso_lnpost", "iso_lnpost_host"
+    _desc = model_desc
 
-    def _scalar_call(self, p, which):
-        """lnpost / lnprior / lnlike of ONE host row as a float: the per-point callback of emcee / MultiNest
-        (reference starmodel.py:797,952,966).  Everything a call needs besides the numbers - the model handle, a
-        parameter buffer, an output buffer, their addresses, the C entry point - is kept between calls and revalidated
-        by two integer comparisons (no prior object anywhere was mutated since; the interpolator was not rebound), so the
-        wrapper adds about a microsecond to the C call (whose resident mailbox wave answers without a launch)."""
-        from . import priors as _p
-        from .interp import TABLE_EPOCH
-        # the cache (and with it the parameter / output buffers) is per THREAD: ctypes drops the GIL inside the C call, so
-        # two threads sharing one pair of buffers would overwrite each other's rows (threaded emcee, a pool around
-        # mnest_loglike); the C side serialises callers of one model on its own mutex
-        tls = self.__dict__.get("_scalar_tls")
-        if tls is None:
-            tls = self.__dict__.setdefault("_scalar_tls", threading.local())
-        c = getattr(tls, "c", None)
-        if (c is None or c[0] != _p.EPOCH[0] or c[1] != self.ic._generation or c[8] != TABLE_EPOCH[0]
-                or c[9] is not self._scalar_cache):
-            device = dev.current_device()
-            h = self.handle(device)                      # the full check (prior objects' versions, interpolator, tables)
-            if self._scalar_cache is None:
-                self._scalar_cache = object()            # token: _dirty() / a rebuilt handle drops every thread's cache
-            buf, out = np.empty(self.n_params), np.empty(3)
-            c = tls.c = (_p.EPOCH[0], self.ic._generation, h, buf, out, buf.ctypes.data,
-                         tuple(out.ctypes.data + 8 * k for k in range(3)), _cabi.lib().iso_lnpost_host,
-                         TABLE_EPOCH[0], self._scalar_cache, self._host_terms())
-        c[3][:] = p                                      # (a row of the wrong length raises here)
-        a = c[6]
-        if c[10]:                                        # priors evaluated on the host (_HostPriorMixin): all parts, then add
-            rc = c[7](c[2], c[5], 1, a[0], a[1], a[2])
-            if rc:
-                _cabi.check(rc)
-            hp = self._host_lnprior(c[10], c[3][None, :])
-            parts = (float(self._host_combine(c[4][0:1], hp)[0]), float(self._host_combine(c[4][1:2], hp)[0]), float(c[4][2]))
-            return parts if which is None else parts[which]
-        if which is None:                                # all three parts in one call: (lnpost, lnprior, lnlike)
-            rc = c[7](c[2], c[5], 1, a[0], a[1], a[2])
-            if rc:
-                _cabi.check(rc)
-            return float(c[4][0]), float(c[4][1]), float(c[4][2])
-        rc = c[7](c[2], c[5], 1, a[0] if which == 0 else None, a[1] if which == 1 else None, a[2] if which == 2 else None)
-        if rc:
-            _cabi.check(rc)
-        return float(c[4][which])
-
-    def handle(self, device=None):
-        if device is None:
-            device = dev.current_device()
-        ich = self.ic.handle(device)
-        h = self._handles.get(device)
-        state = _prior_state(self._priors)
-        if h is not None and (self._handle_ic.get(device) != self.ic._generation or self._handle_state.get(device) != state):
-            _cabi.lib().iso_model_destroy(h)   # the interpolator was rebound / a shared prior object changed: rebuild
-            self._handles.pop(device, None)
-            self._scalar_cache = None
-            h = None
-        if h is None:
-            if -1 in self.ic._prior_cols:
-                raise ValueError("model table lacks the (%s, d%s_deep) columns the EEP prior needs"
-                                 % (self.ic.eep_replaces, "t" if self.ic.eep_replaces == "age" else "m"))
-            desc = self.model_desc()
-            h = C.c_void_p()
-            _cabi.check(_cabi.lib().iso_model_create(ich, C.byref(desc), C.byref(h)))
-            self._handles[device] = h
-            self._handle_ic[device] = self.ic._generation
-            self._handle_state[device] = _prior_state(self._priors)       # packing may have snapped bounds
-        return h
+    def _create(self, ich):
+        if -1 in self.ic._prior_cols:
+            raise ValueError("model table lacks the (%s, d%s_deep) columns the EEP prior needs"
+                             % (self.ic.eep_replaces, "t" if self.ic.eep_replaces == "age" else "m"))
+        return super()._create(ich)
 
     def kernel_path(self, device=None):
         """'generic' | 'fused-compact' | 'fused-packed': the kernel family that evaluates this model on `device`."""
         return ("generic", "fused-compact", "fused-packed")[_cabi.lib().iso_model_kernel_path(self.handle(device))]
 
-    def __del__(self):
-        try:
-            self._dirty()
-        except Exception:
-            pass
-
     def evaluate_device(self, pars, soa=False, parts=False):
         """pars: CUDA float64 tensor, [N, n_params] (or [n_params, N] if soa).
         Returns lnpost[N] or (lnpost, lnprior, lnlike)."""
-        if pars.dim() != 2 or pars.dtype.itemsize != 8 or not pars.dtype.is_floating_point:
-            raise ValueError("pars must be a 2-D float64 tensor")
-        npar = self.n_params
-        if soa:
-            if pars.shape[0] != npar:
-                raise ValueError("expected [%d, N]" % npar)
-            n, stride_n, stride_p = pars.shape[1], 1, pars.shape[1]
-        else:
-            if pars.shape[1] != npar:
-                raise ValueError("expected [N, %d]" % npar)
-            n, stride_n, stride_p = pars.shape[0], npar, 1
-        device = pars.device.index
-        pars = pars.contiguous()
-        post = dev.empty_f64((n,), device)
-        prior = dev.empty_f64((n,), device) if parts else None
-        like = dev.empty_f64((n,), device) if parts else None
-        if n:
-            _cabi.check(_cabi.lib().iso_lnpost(self.handle(device), dev.ptr(pars), stride_n, stride_p, n,
-                                               dev.ptr(post), dev.ptr(prior), dev.ptr(like),
-                                               dev.stream_ptr(device)))
-            terms = self._host_terms()
-            if terms:
-                post, prior = self._host_adjust_tensors(terms, pars.t() if soa else pars, (post, prior))
-        return (post, prior, like) if parts else post
-
-    def _evaluate(self, p, which, soa=False):
-        tp = type(p)
-        if ((tp is list or tp is tuple or (tp is np.ndarray and p.ndim == 1)) and len(p) == self.n_params
-                and not isinstance(p[0], (list, tuple, np.ndarray))):     # (a list of n_params ROWS is a batch)
-            return self._scalar_call(p, which)
-        if dev.is_tensor(p) and p.is_cuda:
-            import torch
-            single = p.dim() == 1
-            pp = p.double()[None, :] if single else p.double()
-            out = self.evaluate_device(pp, soa=soa and not single, parts=which != 0)
-            out = out if which == 0 else out[which]
-            return out[0] if single else out
-        arr = np.ascontiguousarray(p, dtype=np.float64)
-        single = arr.ndim == 1
-        a2 = arr[None, :] if single else arr
-        device = dev.current_device()
-        if not (soa and not single):
-            # host arrays: one C call.  Sampler-callback sizes go through the pinned, device-mapped staging buffer (one
-            # launch, completion flag), large batches through the chunked upload / download pipeline of iso_lnpost_host
-            if a2.shape[1] != self.n_params:
-                raise ValueError("expected [N, %d]" % self.n_params)
-            n = a2.shape[0]
-            out = np.empty(n)
-            ptrs = [None, None, None]
-            ptrs[which] = out.ctypes.data
-            rc = _cabi.lib().iso_lnpost_host(self.handle(device), a2.ctypes.data, n, *ptrs)
-            if rc:
-                _cabi.check(rc)
-            if which != 2:
-                terms = self._host_terms()
-                if terms:
-                    out = self._host_combine(out, self._host_lnprior(terms, a2))
-            return float(out[0]) if single else out
-        out = self.evaluate_device(dev.to_device_f64(a2, device), soa=soa and not single, parts=which != 0)
-        out = (out if which == 0 else out[which]).cpu().numpy()
-        return float(out[0]) if single else out
+        return self._evaluate_device(pars, soa, parts)
 
     def lnpost(self, p, soa=False):
         return self._evaluate(p, 0, soa)
@@ -977,7 +1000,7 @@ class TripleStarModel(BasicStarModel):
 # ==========================================================================================
 # generic (observation-tree) model — "next" row f4
 # ==========================================================================================
-class TreeStarModel(_NestedFitMixin, _ConvenienceMixin, _HostPriorMixin):
+class TreeStarModel(_NestedFitMixin, _ConvenienceMixin, _DeviceModelMixin):
     """The reference's generic ``StarModel`` (isochrones/starmodel.py:63-661): photometry organised
     in an :class:`~isochrones_amd.observation.ObservationTree` (resolved and blended sources,
     relative photometry, several physical systems), evaluated on the device from the flattened
@@ -994,6 +1017,7 @@ class TreeStarModel(_NestedFitMixin, _ConvenienceMixin, _HostPriorMixin):
         from .observation import Observation, ObservationTree, Source
         if ic.eep_replaces != "mass":
             raise NotImplementedError("Prior not implemented for evolution track grids")
+        self._init_device()
         self._ic = ic
         self.name = name
         self.use_emcee = bool(use_emcee)
@@ -1037,7 +1061,6 @@ class TreeStarModel(_NestedFitMixin, _ConvenienceMixin, _HostPriorMixin):
             self.set_bounds(AV=(0, maxAV))
         if max_distance is not None:
             self.set_bounds(distance=(0, max_distance))
-        self._handles, self._handle_ic, self._handle_state = {}, {}, {}
 
     ic = property(lambda self: self._ic)
 
@@ -1273,129 +1296,11 @@ class TreeStarModel(_NestedFitMixin, _ConvenienceMixin, _HostPriorMixin):
         d.eep_lo, d.eep_hi = self._priors["eep"].bounds
         return d
 
-    def _dirty(self):
-        for h in getattr(self, "_handles", {}).values():
-            _cabi.lib().iso_tree_model_destroy(h)
-        self._handles = {}
-        self._handle_ic = {}
-        self._handle_state = {}
-
-    def handle(self, device=None):
-        if device is None:
-            device = dev.current_device()
-        ich = self.ic.handle(device)
-        h = self._handles.get(device)
-        state = _prior_state(self._priors)
-        if h is not None and (self._handle_ic.get(device) != self.ic._generation or self._handle_state.get(device) != state):
-            _cabi.lib().iso_tree_model_destroy(h)
-            self._handles.pop(device, None)
-            h = None
-        if h is None:
-            desc = self.tree_desc()
-            h = C.c_void_p()
-            _cabi.check(_cabi.lib().iso_tree_model_create(ich, C.byref(desc), C.byref(h)))
-            self._handles[device] = h
-            self._handle_ic[device] = self.ic._generation
-            self._handle_state[device] = _prior_state(self._priors)
-        return h
-
-    def __del__(self):
-        try:
-            self._dirty()
-        except Exception:
-            pass
-
-    def evaluate_device(self, pars, parts=False):
-        """pars: CUDA float64 [N, n_params] -> lnpost [N] or (lnpost, lnprior, lnlike)."""
-        npar = self.n_params
-        if pars.dim() != 2 or pars.shape[1] != npar or pars.dtype.itemsize != 8 or not pars.dtype.is_floating_point:
-            raise ValueError("expected a float64 [N, %d] tensor" % npar)
-        device = pars.device.index
-        pars = pars.contiguous()
-        n = pars.shape[0]
-        post = dev.empty_f64((n,), device)
-        prior = dev.empty_f64((n,), device) if parts else None
-        like = dev.empty_f64((n,), device) if parts else None
-        if n:
-            _cabi.check(_cabi.lib().iso_tree_lnpost(self.handle(device), dev.ptr(pars), npar, 1, n, dev.ptr(post),
-                                                    dev.ptr(prior), dev.ptr(like), dev.stream_ptr(device)))
-            terms = self._host_terms()
-            if terms:
-                post, prior = self._host_adjust_tensors(terms, pars, (post, prior))
-        return (post, prior, like) if parts else post
-
-    def _scalar_call(self, p, which):
-        """lnpost / lnprior / lnlike of ONE host row as a float - how emcee / MultiNest drive a generic StarModel
-        (reference starmodel.py:538-542, 797, 952): handle, buffers and addresses are kept per thread and revalidated by
-        integer comparisons (as BasicStarModel._scalar_call); the C call is answered by the model's resident mailbox wave."""
-        from . import priors as _p
-        from .interp import TABLE_EPOCH
-        tls = self.__dict__.get("_scalar_tls")
-        if tls is None:
-            tls = self.__dict__.setdefault("_scalar_tls", threading.local())
-        c = getattr(tls, "c", None)
-        if (c is None or c[0] != _p.EPOCH[0] or c[1] != self.ic._generation or c[8] != TABLE_EPOCH[0]
-                or c[9] is not self._handles.get(c[10])):
-            device = dev.current_device()
-            h = self.handle(device)
-            buf, out = np.empty(self.n_params), np.empty(3)
-            c = tls.c = (_p.EPOCH[0], self.ic._generation, h, buf, out, buf.ctypes.data,
-                         tuple(out.ctypes.data + 8 * k for k in range(3)), _cabi.lib().iso_tree_lnpost_host, TABLE_EPOCH[0], h, device,
-                         self._host_terms())
-        c[3][:] = p
-        a = c[6]
-        if c[11] and which != 2:                         # priors evaluated on the host (_HostPriorMixin)
-            rc = c[7](c[2], c[5], 1, a[0] if which == 0 else None, a[1] if which == 1 else None, None)
-            if rc:
-                _cabi.check(rc)
-            return float(self._host_combine(c[4][which:which + 1], self._host_lnprior(c[11], c[3][None, :]))[0])
-        rc = c[7](c[2], c[5], 1, a[0] if which == 0 else None, a[1] if which == 1 else None, a[2] if which == 2 else None)
-        if rc:
-            _cabi.check(rc)
-        return float(c[4][which])
-
-    def _evaluate(self, p, which):
-        tp = type(p)
-        if ((tp is list or tp is tuple or (tp is np.ndarray and p.ndim == 1)) and len(p) == self.n_params
-                and not isinstance(p[0], (list, tuple, np.ndarray))):
-            return self._scalar_call(p, which)
-        if dev.is_tensor(p) and p.is_cuda:
-            single = p.dim() == 1
-            out = self.evaluate_device(p.double()[None, :] if single else p.double(), parts=which != 0)
-            out = out if which == 0 else out[which]
-            return out[0] if single else out
-        arr = np.ascontiguousarray(p, dtype=np.float64)
-        single = arr.ndim == 1
-        a2 = arr[None, :] if single else arr
-        device = dev.current_device()
-        if a2.ndim == 2 and a2.shape[0] <= 65536:
-            # host arrays of sampler-callback size: one C call through the context's pinned staging buffer
-            if a2.shape[1] != self.n_params:
-                raise ValueError("expected [N, %d]" % self.n_params)
-            n = a2.shape[0]
-            out = np.empty(n)
-            dp = C.POINTER(C.c_double)
-            ptrs = [None, None, None]
-            ptrs[which] = out.ctypes.data_as(dp)
-            _cabi.check(_cabi.lib().iso_tree_lnpost_host(self.handle(device), a2.ctypes.data_as(dp), n, *ptrs))
-            if which != 2:
-                terms = self._host_terms()
-                if terms:
-                    out = self._host_combine(out, self._host_lnprior(terms, a2))
-            return float(out[0]) if single else out
-        out = self.evaluate_device(dev.to_device_f64(a2, device), parts=which != 0)
-        out = (out if which == 0 else out[which]).cpu().numpy()
-        return float(out[0]) if single else out
-
-    def lnpost(self, p):
-        return self._evaluate(p, 0)
-
-    def lnprior(self, p):
-        return self._evaluate(p, 1)
-
-    def lnlike(self, p):
-        return self._evaluate(p, 2)
-
+    # -- device (_DeviceModelMixin) ------------------------------------------------------------
+    _c_create, _c_destroy = "iso_tree_model_create", "iso_tree_model_destroy"
+    _c_lnpost, _c_lnpost_host = "iso_tree_lnpost", "iso_tree_lnpost_host"
+    _desc = tree_desc
+    _host_rows = 65536                   # (beyond: through the device, as one upload and one download)
 
     def prior_transform(self, cube):
         """Unit cube -> parameters (reference: starmodel.py:615-627, its slot walk included: see :meth:`_slots`)."""

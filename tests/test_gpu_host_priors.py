@@ -169,6 +169,61 @@ def test_tree_model_every_system():
     assert mod._host_columns("AV") == [5] and mod._host_columns("age") == [2]
 
 
+class ForeignGauss:
+    """A foreign prior whose ``lnpdf`` leaves the bounds test to the model (the device's flat stand-in applies it)."""
+
+    def __init__(self, mu, sigma, bounds):
+        self.mu, self.sigma, self.bounds = mu, sigma, bounds
+
+    def lnpdf(self, x):
+        return -0.5 * ((x - self.mu) / self.sigma) ** 2
+
+
+@pytest.mark.parametrize("kind", ["single", "tree"])
+def test_one_row_calls_follow_every_change(kind):
+    """The one-row forms keep their handle and buffers between calls (_handles.PreparedCalls).  After each change that
+    makes them stale the one-row lnpost / lnprior / lnlike equal the host-array rows and the CUDA rows bit for bit - also
+    after a host prior's bounds moved in place, which moves no counter: the second row falls out of the new bounds."""
+    import torch
+    if kind == "single":
+        ic = _iso()
+        mod = ia.SingleStarModel(ic, J=(9.6, 0.03), H=(9.2, 0.03), K=(9.1, 0.03), parallax=(8.0, 0.1), Teff=(5700, 100))
+        rows, col, far = [[350.0, 9.6, -0.1, 125.0, 0.2]], 3, ForeignGauss(120.0, 60.0, (0.0, 240.0))
+    else:
+        import bench_configs
+        mod, _ = bench_configs.tree_model_and_samples(16)           # (the resolved binary)
+        ic = mod.ic
+        rows, col, far = [[300.0, 280.0, 9.6, 0.0, 400.0, 0.1]], 4, ForeignGauss(450.0, 100.0, (0.0, 1000.0))
+    rows.append(list(rows[0]))
+    rows[1][col] = 0.8 * far.bounds[1]
+    shared = P.AVPrior()
+    other = ia.SingleStarModel(ic, J=(9.6, 0.03))
+    other.set_prior(AV=shared)
+    mod.set_prior(AV=shared, distance=far)
+    table = ic.model_grid.interp
+    x = np.array(rows)
+    xt = torch.as_tensor(x, device="cuda")
+    fns = (mod.lnpost, mod.lnprior, mod.lnlike)
+    events = (("start", lambda: None),
+              ("set_prior of a device family", lambda: mod.set_prior(feh=P.FehPrior())),
+              ("a shared prior's bounds in place", lambda: setattr(shared, "bounds", (0.0, 0.9))),
+              ("set_bounds", lambda: mod.set_bounds(AV=(0.0, 0.8))),
+              ("a host prior's bounds in place", lambda: setattr(far, "bounds", (0.0, 0.6 * far.bounds[1]))),
+              ("add_column", lambda: table.add_column(np.zeros(table.grid.shape[:-1]), "extra")),
+              ("ic.release()", ic.release))
+    for what, event in events:
+        before = np.array([[fn(r) for fn in fns] for r in rows])    # (prepared before the change)
+        event()
+        one = np.array([[fn(r) for fn in fns] for r in rows])
+        assert np.isfinite(one[0]).all(), what
+        for form, got in (("host array", [fn(x) for fn in fns]), ("CUDA", [fn(xt).cpu().numpy() for fn in fns])):
+            got = np.array(got).T
+            assert np.array_equal(got.view(np.int64), one.view(np.int64)), (what, form, got, one)
+        if what == "a host prior's bounds in place":
+            assert np.isfinite(before[1, 0]) and one[1, 0] == -np.inf  # (the second row left the new bounds)
+    assert mod._scalar_call(rows[0], None) == tuple(one[0])
+
+
 def test_fits_take_the_framework_sampler_and_the_kernels_refuse():
     from isochrones_amd.sampler import EnsembleSampler, FusedEnsembleSampler
     ic = _iso()
