@@ -1,4 +1,4 @@
-// Resident mailbox kernel for the per-point callback: the reference is driven one lnpost(p) at a time by emcee / MultiNest
+// Resident mailbox kernel for the per-point callback (the protocol of the resident waves: fast/resident_wave.h): the reference is driven one lnpost(p) at a time by emcee / MultiNest
 // (isochrones/starmodel.py:797,952,966), and a launch per call costs ~20 us of which the evaluation is ~4.  Here ONE wave
 // stays resident on a CU for the model and polls a 64-byte request line in pinned, device-mapped host memory:
 //
@@ -25,15 +25,6 @@
 namespace iso {
 namespace fastk {
 
-__device__ __forceinline__ unsigned long long sys_load(const unsigned long long* p)
-{
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ __forceinline__ void sys_store(unsigned long long* p, unsigned long long v)
-{
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 template <int KIND, int NS, int NB>
 __global__ __launch_bounds__(64, 2) void k_mailbox_lnpost(const FastArgs A0, IsoMailbox* mb, unsigned long long idle_ticks,
                                                           unsigned long long life_ticks)
@@ -45,16 +36,12 @@ __global__ __launch_bounds__(64, 2) void k_mailbox_lnpost(const FastArgs A0, Iso
     const int lane = (int)threadIdx.x;
     typedef const __attribute__((address_space(4))) DevModel* const_model_ptr;
     constexpr int NP = NS + 4;
-    unsigned long long last = sys_load(&mb->done[0]);         // what the previous resident wave (or nobody) finished last
-    const unsigned long long t_start = wall_clock64();
-    unsigned long long t_idle = t_start;
+    WaveLoop<IsoMailbox> W(mb, idle_ticks, life_ticks);
     for (;;) {
         const unsigned long long w = sys_load(&mb->req[lane & 7]);
         const unsigned long long seq = __shfl(w, 0);
-        if (seq == last) {
-            const unsigned long long now = wall_clock64();
-            const bool leave = (now - t_idle > idle_ticks) | (now - t_start > life_ticks) | (sys_load(&mb->ctl[1]) != 0);
-            if (leave) break;                                  // (wave-uniform: every lane read the same words)
+        if (seq == W.last) {
+            if (W.leave()) break;
             continue;
         }
         // the argument block is read again from the kernel-argument segment for every request (scalar loads where a field is
@@ -108,13 +95,9 @@ __global__ __launch_bounds__(64, 2) void k_mailbox_lnpost(const FastArgs A0, Iso
 #ifdef ISO_MAILBOX_CLOCK
         if (lane == 0) sys_store(&mb->done[4], wall_clock64() - t_seen);
 #endif
-        __threadfence_system();                                // results before the sequence word
-        if (lane == 0) sys_store(&mb->done[0], seq);
-        last = seq;
-        t_idle = wall_clock64();
+        W.answered(seq, lane);
     }
-    __threadfence_system();
-    if (lane == 0) sys_store(reinterpret_cast<unsigned long long*>(&mb->ctl[0]), 2ull);      // state: exited
+    W.exit(lane);
 }
 
 template <int KIND, int NS>

@@ -77,21 +77,15 @@ __global__ __launch_bounds__(64, 2) void k_mailbox_tree(const FastArgs A, const 
     // same, for 7 KB - profiles/r06/tree_mailbox_record_ab.txt)
     typedef const __attribute__((address_space(4))) DevTree* const_tree_ptr;
     const DevTree& T = *(const DevTree*)((const_tree_ptr)(uintptr_t)Tp);
-    auto sys_load = [](const unsigned long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); };
-    auto sys_store = [](unsigned long long* p, unsigned long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); };
-    unsigned long long last = sys_load(&mb->done[0]);
-    const unsigned long long t_start = wall_clock64();
-    unsigned long long t_idle = t_start;
+    WaveLoop<IsoTreeBox> W(mb, idle_ticks, life_ticks);
     const int np = T.n_params;
     for (;;) {
         const unsigned long long w = sys_load(&mb->req[lane & 31]);
         const int wlo = (int)(unsigned)(w & 0xFFFFFFFFull), whi = (int)(unsigned)(w >> 32);
         const unsigned long long seq = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(whi, 0) << 32) |
                                        (unsigned long long)(unsigned)__builtin_amdgcn_readlane(wlo, 0);
-        if (seq == last) {
-            const unsigned long long now = wall_clock64();
-            const bool leave = (now - t_idle > idle_ticks) | (now - t_start > life_ticks) | (sys_load(&mb->ctl[1]) != 0);
-            if (leave) break;                              // (wave-uniform)
+        if (seq == W.last) {
+            if (W.leave()) break;
             continue;
         }
 #ifdef ISO_MAILBOX_CLOCK
@@ -105,13 +99,7 @@ __global__ __launch_bounds__(64, 2) void k_mailbox_tree(const FastArgs A, const 
             return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(whi, 1 + j) << 32) |
                    (unsigned long long)(unsigned)__builtin_amdgcn_readlane(wlo, 1 + j);
         };
-        uint32_t c = 0x9E3779B9u;                          // mailbox_checksum (iso_internal.h) over the np parameter words
-        for (int q = 0; q < np; ++q) {
-            const unsigned long long x = word(q);
-            c = (c ^ (uint32_t)x) * 0x85EBCA6Bu;
-            c = (c ^ (uint32_t)(x >> 32)) * 0xC2B2AE35u + (uint32_t)q;
-        }
-        if (c != (uint32_t)(seq >> 32)) continue;          // the lines did not arrive together: poll again
+        if (mailbox_checksum(np, word) != (uint32_t)(seq >> 32)) continue;      // the lines did not arrive together: poll again
         const bool parts = ((seq >> 8) & 1) != 0;
         // the parameters go through LDS and are read from there as the batch kernel reads them from memory: plain loads, so
         // that the evaluation is the same expression tree in both kernels (with the words taken straight from the request
@@ -141,13 +129,9 @@ __global__ __launch_bounds__(64, 2) void k_mailbox_tree(const FastArgs A, const 
 #endif
 #endif
         }
-        __threadfence_system();                            // results before the sequence word
-        if (lane == 0) sys_store(&mb->done[0], seq);
-        last = seq;
-        t_idle = wall_clock64();
+        W.answered(seq, lane);
     }
-    __threadfence_system();
-    if (lane == 0) sys_store(&mb->ctl[0], 2ull);          // state: exited
+    W.exit(lane);
 }
 
 }  // namespace fastk

@@ -301,12 +301,7 @@ struct iso_tree_model {
     double* d_axes_blob;
     bool fast_ok;
     FastArgs fast;
-    // resident mailbox wave of the per-point callback (lazy; calls are serialised by the context's stage_mu)
-    iso::IsoTreeBox* mbox;   // pinned, device-mapped
-    iso::IsoTreeBox* d_mbox;
-    hipStream_t mbox_stream;
-    unsigned long long mbox_count;
-    int mbox_state;          // 0 untried, 1 usable, -1 not available
+    iso::ResidentWave<iso::IsoTreeBox> mbox;   // the per-point callback's resident wave (lazy; serialised by the context's stage_mu)
 };
 
 struct iso_eep_table {
@@ -361,10 +356,116 @@ int ensure_wide_pack(iso_table* t, int64_t n)
 
 }  // namespace
 
+// ---- the scalar accessors through the context's resident service wave (kernels/k_service.h) ------------------------------------
+// ISOCHRONES_AMD_MAILBOX=0 keeps every call on the launch path (as for the per-point lnpost callback).
 namespace {
-// the resident service wave of the scalar accessors (defined with the *_host entry points below)
-void service_stop(iso_ctx* ctx, bool release);
-void service_forget(const void* key);
+struct SvcTargetRec {
+    SvcTarget* d_target;
+};
+std::mutex g_svc_mu;                                             // guards the two maps below (calls are serialised per context
+std::unordered_map<iso_ctx*, ResidentWave<IsoSvcBox>> g_services;   // by ctx->stage_mu, which every *_host entry point holds)
+std::unordered_map<const void*, SvcTargetRec> g_svc_targets;     // iso_table* / iso_ic* / iso_eep_table* -> its device record
+
+// the context's service wave (its box made on first use); null = none for this context
+ResidentWave<IsoSvcBox>* service_of(iso_ctx* ctx)
+{
+    std::lock_guard<std::mutex> lock(g_svc_mu);
+    ResidentWave<IsoSvcBox>& sv = g_services[ctx];
+    const bool ok = sv.ready([] {
+        if (hipFuncSetAttribute((const void*)k_service, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(ISO_SVC_LDS_DOUBLES * sizeof(double))) == hipSuccess)
+            return true;
+        (void)hipGetLastError();
+        return false;
+    });
+    return ok ? &sv : nullptr;
+}
+
+// ask the context's wave to leave and wait until it has; `release` frees the mailbox
+void service_stop(iso_ctx* ctx, bool release)
+{
+    ResidentWave<IsoSvcBox> gone;
+    ResidentWave<IsoSvcBox>* sv = &gone;
+    {
+        std::lock_guard<std::mutex> lock(g_svc_mu);
+        auto it = g_services.find(ctx);
+        if (it == g_services.end()) return;
+        if (release) {
+            gone = it->second;
+            g_services.erase(it);
+        } else {
+            sv = &it->second;
+        }
+    }
+    sv->stop(release);
+}
+
+// the device record of a target (created on first use); 0 = could not be created
+bool service_target(const void* key, const SvcTarget& host, SvcTargetRec* out)
+{
+    std::lock_guard<std::mutex> lock(g_svc_mu);
+    auto it = g_svc_targets.find(key);
+    if (it != g_svc_targets.end()) {
+        *out = it->second;
+        return true;
+    }
+    SvcTargetRec rec;
+    if (hipMalloc(reinterpret_cast<void**>(&rec.d_target), sizeof(SvcTarget)) != hipSuccess ||
+        hipMemcpy(rec.d_target, &host, sizeof(SvcTarget), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    g_svc_targets[key] = rec;
+    *out = rec;
+    return true;
+}
+
+// (before the object's tables are freed)
+void service_forget(const void* key)
+{
+    SvcTargetRec rec{nullptr};
+    {
+        std::lock_guard<std::mutex> lock(g_svc_mu);
+        auto it = g_svc_targets.find(key);
+        if (it == g_svc_targets.end()) return;
+        rec = it->second;
+        g_svc_targets.erase(it);
+    }
+    (void)hipFree(rec.d_target);      // (a device-wide wait: a resident wave has left by its idle time-out)
+}
+
+// one request; ISO_OK, or 1 = not served (the caller launches instead).  Caller holds ctx->stage_mu.
+int service_call(iso_ctx* ctx, int op, const SvcTargetRec& tgt, const double* x, int nx, const int32_t* cols, int k, double* out,
+                 int nout)
+{
+    ResidentWave<IsoSvcBox>* sv = service_of(ctx);
+    if (!sv) return 1;
+    IsoSvcBox* mb = sv->box;
+    unsigned long long words[10];
+    std::memset(words, 0, sizeof words);
+    words[0] = (unsigned long long)(uintptr_t)tgt.d_target;
+    for (int q = 0; q < nx; ++q) std::memcpy(&words[1 + q], x + q, 8);
+    for (int c = 0; c < k; ++c) words[6 + (c >> 3)] |= (unsigned long long)(cols[c] & 0xFF) << (8 * (c & 7));
+    const unsigned long long seq = ((unsigned long long)mailbox_checksum(words, 10) << 32) | ((++sv->count & 0xFFFFull) << 16) |
+                                   ((unsigned long long)k << 8) | (unsigned long long)op;
+    if (k > 8)
+        for (int q = 7; q < 10; ++q) __atomic_store_n(&mb->req[1 + q], words[q], __ATOMIC_RELAXED);    // behind the line, before it
+    for (int q = 0; q < 7; ++q) __atomic_store_n(&mb->req[1 + q], words[q], __ATOMIC_RELAXED);
+    const bool served = sv->call(seq, [](IsoSvcBox* d_mb, unsigned long long idle, unsigned long long life, hipStream_t s) {
+        note_kernel("k_service");
+        hipLaunchKernelGGL(k_service, dim3(1), dim3(64), (size_t)ISO_SVC_LDS_DOUBLES * sizeof(double), s, d_mb, idle, life);
+        return true;
+    });
+    if (!served) return 1;
+    for (int q = 0; q < nout; ++q) {
+        const unsigned long long w = __atomic_load_n(reinterpret_cast<unsigned long long*>(&mb->out[q]), __ATOMIC_RELAXED);
+        std::memcpy(out + q, &w, 8);
+    }
+    return ISO_OK;
+}
+}  // namespace
+
+namespace {
 void free_mag_pack(MagPack& mp);
 int acquire_mag_pack(iso_ic* ic, const int32_t* bc_cols, int nb, int64_t n, iso::FastArgs& F);
 hipError_t acquire_band_pack(iso_ic* ic, const int32_t* bc_cols, int nb, std::shared_ptr<BandPack>* out, bool* ok);
@@ -1131,10 +1232,6 @@ int iso_model_create(iso_ic* ic, const iso_model_desc* desc, iso_model** out)
     m->d_axes_blob = nullptr;
     m->fast_ok = false;
     m->h_stage = nullptr;
-    m->mbox = m->d_mbox = nullptr;
-    m->mbox_stream = nullptr;
-    m->mbox_count = 0;
-    m->mbox_state = 0;
     m->stage_rows = 0;
     m->stage_seq = 0;
     m->d_pipe = nullptr;
@@ -1205,13 +1302,11 @@ int iso_model_create(iso_ic* ic, const iso_model_desc* desc, iso_model** out)
     return ISO_OK;
 }
 
-void mailbox_stop(iso_model* m, bool release);
-
 void iso_model_destroy(iso_model* m)
 {
     if (!m) return;
     DeviceGuard guard(m->device);
-    mailbox_stop(m, true);            // the resident wave reads the tables below (and hipFree would wait for it anyway)
+    m->mbox.stop(true);               // the resident wave reads the tables below (and hipFree would wait for it anyway)
     if (m->d_model) (void)hipFree(m->d_model);
     if (m->d_bc_hot) (void)hipFree(m->d_bc_hot);
     if (m->d_bcq) (void)hipFree(m->d_bcq);
@@ -1457,100 +1552,29 @@ static int lnpost_host_pipelined(iso_model* m, const double* pars, int64_t n, do
     return ISO_OK;
 }
 
-// ---- the per-point callback through the model's resident mailbox wave (iso_fast_mailbox.hip) --------------------------------
-// ISOCHRONES_AMD_MAILBOX=0 keeps every call on the launch path; ISOCHRONES_AMD_MAILBOX_IDLE_US (default 1000) is how long the
-// wave stays without a request - the longest a device-wide synchronise elsewhere in the process can be held up by it.
+// ---- the per-point callback through the model's resident mailbox wave (iso_fast_mailbox.hip; fast/resident_wave.h) ----------
 namespace {
-constexpr double WALL_CLOCK_HZ = 1.0e8;          // wall_clock64(): the constant 100 MHz counter
-
-inline unsigned long long mb_load(const volatile unsigned long long* p)
-{
-    return __atomic_load_n(p, __ATOMIC_ACQUIRE);
-}
-
-bool mailbox_enabled()
-{
-    const char* e = std::getenv("ISOCHRONES_AMD_MAILBOX");
-    return !(e && e[0] == '0');
-}
-
-bool mailbox_launch(iso_model* m)
-{
-    double idle_us = 1000.0;
-    if (const char* e = std::getenv("ISOCHRONES_AMD_MAILBOX_IDLE_US")) idle_us = std::max(10.0, std::atof(e));
-    const unsigned long long idle = (unsigned long long)(idle_us * 1e-6 * WALL_CLOCK_HZ);
-    const unsigned long long life = (unsigned long long)(30.0 * WALL_CLOCK_HZ);       // 30 s whatever happens
-    __atomic_store_n(&m->mbox->ctl[1], 0ull, __ATOMIC_RELAXED);
-    __atomic_store_n(&m->mbox->ctl[0], 1ull, __ATOMIC_RELEASE);                    // running (the wave writes 2 when it leaves)
-    if (!launch_mailbox(m->ic->kind, m->desc.n_stars, m->desc.n_bands, m->fast, m->d_mbox, idle, life, m->mbox_stream) ||
-        hipGetLastError() != hipSuccess) {
-        __atomic_store_n(&m->mbox->ctl[0], 2ull, __ATOMIC_RELEASE);
-        return false;
-    }
-    return true;
-}
-
-// lazily: the pinned mailbox, its stream; false = this model has no mailbox (the caller takes the launch path)
-bool mailbox_ready(iso_model* m)
-{
-    if (m->mbox_state < 0) return false;
-    if (m->mbox_state > 0) return true;
-    m->mbox_state = -1;
-    if (!m->fast_ok || !m->fast.hotq || (!m->fast.bcq && m->desc.n_bands > 0) || m->fast.astq || m->desc.n_bands > FAST_NB_MAX) return false;
-    if (hipHostMalloc(reinterpret_cast<void**>(&m->mbox), sizeof(IsoMailbox), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-        (void)hipGetLastError();
-        m->mbox = nullptr;
-        return false;
-    }
-    std::memset(m->mbox, 0, sizeof(IsoMailbox));
-    m->mbox->ctl[0] = 2;                             // no wave yet
-    if (hipHostGetDevicePointer(reinterpret_cast<void**>(&m->d_mbox), m->mbox, 0) != hipSuccess ||
-        hipStreamCreateWithFlags(&m->mbox_stream, hipStreamNonBlocking) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipHostFree(m->mbox);
-        m->mbox = nullptr;
-        return false;
-    }
-    m->mbox_state = 1;
-    return true;
-}
-
 // n <= ISO_MAILBOX_ROWS rows through the resident wave; ISO_OK, or 1 = not served (the caller launches instead)
 int mailbox_call(iso_model* m, const double* pars, int n, double* lnpost_out, double* lnprior_out, double* lnlike_out)
 {
-    IsoMailbox* mb = m->mbox;
+    IsoMailbox* mb = m->mbox.box;
     const int np_ = m->desc.n_stars + 4;
     const bool parts = lnprior_out || lnlike_out;
-    unsigned long long seq = ((++m->mbox_count & 0xFFFFull) << 16) | ((unsigned long long)parts << 8) | (unsigned long long)(n - 1);
+    unsigned long long seq = ((++m->mbox.count & 0xFFFFull) << 16) | ((unsigned long long)parts << 8) | (unsigned long long)(n - 1);
     if (n == 1) {
         unsigned long long words[ISO_MAX_PARAMS];
         for (int q = 0; q < np_; ++q) {
             std::memcpy(&words[q], pars + q, 8);
             __atomic_store_n(&mb->req[1 + q], words[q], __ATOMIC_RELAXED);
         }
-        // the wave accepts the request only with parameter words that give this number: a line read in pieces (new sequence
-        // word, old parameters) is polled again instead of evaluated
         seq |= (unsigned long long)mailbox_checksum(words, np_) << 32;
     } else {
         std::memcpy(mb->rows, pars, sizeof(double) * (size_t)n * np_);
     }
-    __atomic_store_n(&mb->req[0], seq, __ATOMIC_RELEASE);        // the sequence word last
-    if (mb_load(&mb->ctl[0]) != 1 && !mailbox_launch(m)) return 1;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (uint64_t spins = 1; mb_load(&mb->done[0]) != seq; ++spins) {
-        if ((spins & 255) == 0) {
-            // the wave may have left (idle / lifetime) between our look at the state and its last poll: start another one,
-            // which finds the request waiting.  A wave that neither answers nor leaves within 2 s is a fault.
-            if (mb_load(&mb->ctl[0]) == 2 && mb_load(&mb->done[0]) != seq) {
-                if (!mailbox_launch(m)) return 1;
-            } else if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-                __atomic_store_n(&mb->ctl[1], 1ull, __ATOMIC_RELEASE);
-                (void)hipStreamSynchronize(m->mbox_stream);
-                m->mbox_state = -1;
-                return 1;
-            }
-        }
-    }
+    const bool served = m->mbox.call(seq, [m](IsoMailbox* d_mb, unsigned long long idle, unsigned long long life, hipStream_t s) {
+        return launch_mailbox(m->ic->kind, m->desc.n_stars, m->desc.n_bands, m->fast, d_mb, idle, life, s);
+    });
+    if (!served) return 1;
     if (n == 1) {
         double r[3];
         for (int k = 0; k < 3; ++k) {
@@ -1560,15 +1584,8 @@ int mailbox_call(iso_model* m, const double* pars, int n, double* lnpost_out, do
         if (lnpost_out) *lnpost_out = r[0];
         if (lnprior_out) *lnprior_out = r[1];
         if (lnlike_out) *lnlike_out = r[2];
-#ifdef ISO_MAILBOX_CLOCK        // (variant builds: the wave's own time from seeing a request to its results, 100 MHz ticks)
-        {
-            static unsigned long long calls = 0, ticks = 0;
-            ticks += __atomic_load_n(&mb->done[4], __ATOMIC_RELAXED);
-            if (++calls % 2000 == 0) {
-                std::fprintf(stderr, "model mailbox: %.2f us on the device per call (%llu calls)\n", ticks * 0.01 / (double)calls, calls);
-                calls = ticks = 0;
-            }
-        }
+#ifdef ISO_MAILBOX_CLOCK
+        m->mbox.clock("model mailbox");
 #endif
     } else {
         if (lnpost_out) std::memcpy(lnpost_out, mb->out, sizeof(double) * n);
@@ -1577,26 +1594,20 @@ int mailbox_call(iso_model* m, const double* pars, int n, double* lnpost_out, do
     }
     return ISO_OK;
 }
-}  // namespace
 
-// ask the model's resident wave to leave and wait until it has (before its tables go, or before a device-wide synchronise
-// that should not wait for the idle timeout); frees the mailbox when `release`
-void mailbox_stop(iso_model* m, bool release)
+// Spin on a completion flag in mapped memory until it reads `seq`.  A kernel that never raises it (a fault, a very large
+// batch) must not hang the caller: after 2 ms this gives up, and the caller synchronises the stream, which also reports the
+// error.  true = seen.
+bool wait_flag(const volatile unsigned long long* flag, unsigned long long seq)
 {
-    if (!m->mbox) return;
-    if (mb_load(&m->mbox->ctl[0]) == 1) {
-        __atomic_store_n(&m->mbox->ctl[1], 1ull, __ATOMIC_RELEASE);
-        (void)hipStreamSynchronize(m->mbox_stream);
-    }
-    if (release) {
-        (void)hipStreamSynchronize(m->mbox_stream);
-        (void)hipStreamDestroy(m->mbox_stream);
-        (void)hipHostFree(m->mbox);
-        m->mbox = m->d_mbox = nullptr;
-        m->mbox_stream = nullptr;
-        m->mbox_state = 0;
-    }
+    const auto t0 = std::chrono::steady_clock::now();
+    bool seen = false;
+    for (uint64_t spins = 0; !(seen = (*flag == seq)); ++spins)
+        if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return seen;
 }
+}  // namespace
 
 int iso_lnpost_host(iso_model* m, const double* pars, int64_t n, double* lnpost_out, double* lnprior_out,
                     double* lnlike_out)
@@ -1609,7 +1620,10 @@ int iso_lnpost_host(iso_model* m, const double* pars, int64_t n, double* lnpost_
     std::lock_guard<std::mutex> lock(m->host_mu);       // ctypes drops the GIL: two Python threads may call one model
     const int np_ = m->desc.n_stars + 4;
     // a sampler's per-point callback (one row, or a few): the model's resident mailbox wave - no launch
-    if (n <= ISO_MAILBOX_ROWS && mailbox_enabled() && mailbox_ready(m)) {
+    const bool mbox_ok = n <= ISO_MAILBOX_ROWS && resident_waves_enabled() && m->mbox.ready([m] {
+        return m->fast_ok && m->fast.hotq && (m->fast.bcq || m->desc.n_bands <= 0) && !m->fast.astq && m->desc.n_bands <= FAST_NB_MAX;
+    });
+    if (mbox_ok) {
         const int rc = mailbox_call(m, pars, (int)n, lnpost_out, lnprior_out, lnlike_out);
         if (rc <= 0) return rc;
     }
@@ -1647,17 +1661,7 @@ int iso_lnpost_host(iso_model* m, const double* pars, int64_t n, double* lnpost_
         const int rc = enqueue_lnpost(m, d_pars, np_, 1, c, lnpost_out ? d_post : nullptr, lnprior_out ? d_prior : nullptr,
                                       lnlike_out ? d_like : nullptr, nullptr, flagged ? d_flag : nullptr, seq);
         if (rc != ISO_OK) return rc;
-        bool seen = false;
-        if (flagged) {
-            const auto t0 = std::chrono::steady_clock::now();
-            for (uint64_t spins = 0; !(seen = (*h_flag == seq)); ++spins) {
-                // a kernel that never raises the flag (a fault) must not hang the caller: after 2 ms fall back to the
-                // stream synchronise, which also reports the error
-                if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-            }
-            std::atomic_thread_fence(std::memory_order_acquire);
-        }
-        if (!seen) HIP_TRY(hipStreamSynchronize(nullptr));
+        if (!(flagged && wait_flag(h_flag, seq))) HIP_TRY(hipStreamSynchronize(nullptr));
         if (lnpost_out) std::memcpy(lnpost_out + done, h_post, sizeof(double) * c);
         if (lnprior_out) std::memcpy(lnprior_out + done, h_prior, sizeof(double) * c);
         if (lnlike_out) std::memcpy(lnlike_out + done, h_like, sizeof(double) * c);
@@ -1759,172 +1763,6 @@ int iso_interp_eep(iso_eep_table* t, const double* x, const double* x0, const do
 }
 
 
-// ---- the scalar accessors through the context's resident service wave (kernels/k_service.h) ------------------------------------
-// ISOCHRONES_AMD_MAILBOX=0 keeps every call on the launch path (as for the per-point lnpost callback).
-namespace {
-struct SvcTargetRec {
-    SvcTarget* d_target;
-};
-struct iso_service {
-    IsoSvcBox* box = nullptr;      // pinned, device-mapped
-    IsoSvcBox* d_box = nullptr;
-    hipStream_t stream = nullptr;
-    unsigned long long count = 0;
-    int state = 0;                 // 0 untried, 1 usable, -1 not available
-};
-std::mutex g_svc_mu;                                             // guards the two maps below (calls are serialised per context
-std::unordered_map<iso_ctx*, iso_service*> g_services;           // by ctx->stage_mu, which every *_host entry point holds)
-std::unordered_map<const void*, SvcTargetRec> g_svc_targets;     // iso_table* / iso_ic* / iso_eep_table* -> its device record
-
-inline unsigned long long svc_host_load(const volatile unsigned long long* p) { return __atomic_load_n(p, __ATOMIC_ACQUIRE); }
-
-bool service_enabled()
-{
-    const char* e = std::getenv("ISOCHRONES_AMD_MAILBOX");
-    return !(e && e[0] == '0');
-}
-
-iso_service* service_of(iso_ctx* ctx)
-{
-    std::lock_guard<std::mutex> lock(g_svc_mu);
-    iso_service*& sv = g_services[ctx];
-    if (!sv) sv = new iso_service();
-    if (sv->state != 0) return sv->state > 0 ? sv : nullptr;
-    sv->state = -1;
-    if (hipHostMalloc(reinterpret_cast<void**>(&sv->box), sizeof(IsoSvcBox), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-        (void)hipGetLastError();
-        sv->box = nullptr;
-        return nullptr;
-    }
-    std::memset(sv->box, 0, sizeof(IsoSvcBox));
-    sv->box->ctl[0] = 2;                                         // no wave yet
-    if (hipHostGetDevicePointer(reinterpret_cast<void**>(&sv->d_box), sv->box, 0) != hipSuccess ||
-        hipStreamCreateWithFlags(&sv->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_service, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(ISO_SVC_LDS_DOUBLES * sizeof(double))) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipHostFree(sv->box);
-        sv->box = nullptr;
-        return nullptr;
-    }
-    sv->state = 1;
-    return sv;
-}
-
-bool service_launch(iso_service* sv)
-{
-    double idle_us = 1000.0;
-    if (const char* e = std::getenv("ISOCHRONES_AMD_MAILBOX_IDLE_US")) idle_us = std::max(10.0, std::atof(e));
-    const unsigned long long idle = (unsigned long long)(idle_us * 1e-6 * 1.0e8);       // wall_clock64(): 100 MHz
-    const unsigned long long life = (unsigned long long)(30.0 * 1.0e8);
-    __atomic_store_n(&sv->box->ctl[1], 0ull, __ATOMIC_RELAXED);
-    __atomic_store_n(&sv->box->ctl[0], 1ull, __ATOMIC_RELEASE);
-    note_kernel("k_service");
-    hipLaunchKernelGGL(k_service, dim3(1), dim3(64), (size_t)ISO_SVC_LDS_DOUBLES * sizeof(double), sv->stream, sv->d_box, idle, life);
-    if (hipGetLastError() != hipSuccess) {
-        __atomic_store_n(&sv->box->ctl[0], 2ull, __ATOMIC_RELEASE);
-        return false;
-    }
-    return true;
-}
-
-// ask the context's wave to leave and wait until it has; `release` frees the mailbox
-void service_stop(iso_ctx* ctx, bool release)
-{
-    iso_service* sv = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(g_svc_mu);
-        auto it = g_services.find(ctx);
-        if (it == g_services.end()) return;
-        sv = it->second;
-        if (release) g_services.erase(it);
-    }
-    if (sv->box) {
-        if (svc_host_load(&sv->box->ctl[0]) == 1) __atomic_store_n(&sv->box->ctl[1], 1ull, __ATOMIC_RELEASE);
-        (void)hipStreamSynchronize(sv->stream);
-    }
-    if (release) {
-        if (sv->box) {
-            (void)hipStreamDestroy(sv->stream);
-            (void)hipHostFree(sv->box);
-        }
-        delete sv;
-    }
-}
-
-// the device record of a target (created on first use); 0 = could not be created
-bool service_target(const void* key, const SvcTarget& host, SvcTargetRec* out)
-{
-    std::lock_guard<std::mutex> lock(g_svc_mu);
-    auto it = g_svc_targets.find(key);
-    if (it != g_svc_targets.end()) {
-        *out = it->second;
-        return true;
-    }
-    SvcTargetRec rec;
-    if (hipMalloc(reinterpret_cast<void**>(&rec.d_target), sizeof(SvcTarget)) != hipSuccess ||
-        hipMemcpy(rec.d_target, &host, sizeof(SvcTarget), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    g_svc_targets[key] = rec;
-    *out = rec;
-    return true;
-}
-
-// (before the object's tables are freed)
-void service_forget(const void* key)
-{
-    SvcTargetRec rec{nullptr};
-    {
-        std::lock_guard<std::mutex> lock(g_svc_mu);
-        auto it = g_svc_targets.find(key);
-        if (it == g_svc_targets.end()) return;
-        rec = it->second;
-        g_svc_targets.erase(it);
-    }
-    (void)hipFree(rec.d_target);      // (a device-wide wait: a resident wave has left by its idle time-out)
-}
-
-// one request; ISO_OK, or 1 = not served (the caller launches instead).  Caller holds ctx->stage_mu.
-int service_call(iso_ctx* ctx, int op, const SvcTargetRec& tgt, const double* x, int nx, const int32_t* cols, int k, double* out,
-                 int nout)
-{
-    iso_service* sv = service_of(ctx);
-    if (!sv) return 1;
-    IsoSvcBox* mb = sv->box;
-    unsigned long long words[10];
-    std::memset(words, 0, sizeof words);
-    words[0] = (unsigned long long)(uintptr_t)tgt.d_target;
-    for (int q = 0; q < nx; ++q) std::memcpy(&words[1 + q], x + q, 8);
-    for (int c = 0; c < k; ++c) words[6 + (c >> 3)] |= (unsigned long long)(cols[c] & 0xFF) << (8 * (c & 7));
-    const unsigned long long seq = ((unsigned long long)mailbox_checksum(words, 10) << 32) | ((++sv->count & 0xFFFFull) << 16) |
-                                   ((unsigned long long)k << 8) | (unsigned long long)op;
-    if (k > 8)
-        for (int q = 7; q < 10; ++q) __atomic_store_n(&mb->req[1 + q], words[q], __ATOMIC_RELAXED);    // behind the line, before it
-    for (int q = 0; q < 7; ++q) __atomic_store_n(&mb->req[1 + q], words[q], __ATOMIC_RELAXED);
-    __atomic_store_n(&mb->req[0], seq, __ATOMIC_RELEASE);        // the sequence word last
-    if (svc_host_load(&mb->ctl[0]) != 1 && !service_launch(sv)) return 1;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (uint64_t spins = 1; svc_host_load(&mb->done[0]) != seq; ++spins) {
-        if ((spins & 255) == 0) {
-            if (svc_host_load(&mb->ctl[0]) == 2 && svc_host_load(&mb->done[0]) != seq) {
-                if (!service_launch(sv)) return 1;               // the wave left between our look at its state and its last poll
-            } else if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-                __atomic_store_n(&mb->ctl[1], 1ull, __ATOMIC_RELEASE);
-                (void)hipStreamSynchronize(sv->stream);
-                sv->state = -1;
-                return 1;
-            }
-        }
-    }
-    for (int q = 0; q < nout; ++q) {
-        const unsigned long long w = __atomic_load_n(reinterpret_cast<unsigned long long*>(&mb->out[q]), __ATOMIC_RELAXED);
-        std::memcpy(out + q, &w, 8);
-    }
-    return ISO_OK;
-}
-}  // namespace
-
 namespace {
 // the context's pinned, device-mapped staging area (host view + device view); caller holds ctx->stage_mu
 int ctx_stage(iso_ctx* ctx, double** host, double** dev)
@@ -1963,12 +1801,7 @@ int ctx_wait(iso_ctx* ctx, double* h, double* d)
     hipLaunchKernelGGL(k_signal_done, dim3(1), dim3(1), 0, nullptr,
                        reinterpret_cast<volatile unsigned long long*>(d + ISO_CTX_STAGE_DOUBLES), seq);
     HIP_TRY(hipGetLastError());
-    const auto t0 = std::chrono::steady_clock::now();
-    bool seen = false;
-    for (uint64_t spins = 0; !(seen = (*h_flag == seq)); ++spins)
-        if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-    std::atomic_thread_fence(std::memory_order_acquire);
-    if (!seen) HIP_TRY(hipStreamSynchronize(nullptr));
+    if (!wait_flag(h_flag, seq)) HIP_TRY(hipStreamSynchronize(nullptr));
     return ISO_OK;
 }
 }  // namespace
@@ -1981,7 +1814,7 @@ int iso_interp_host(iso_table* t, const double* x, int64_t n, const int32_t* ico
     if (n == 0) return ISO_OK;
     DeviceGuard guard(t->device);
     std::lock_guard<std::mutex> lock(t->ctx->stage_mu);
-    if (n == 1 && k <= ISO_SVC_MAX_COLS && t->shape[t->ndim] <= 256 && service_enabled()) {
+    if (n == 1 && k <= ISO_SVC_MAX_COLS && t->shape[t->ndim] <= 256 && resident_waves_enabled()) {
         // one point: the context's resident service wave - no launch (kernels/k_service.h)
         bool cols_ok = true;
         for (int c = 0; c < k; ++c) cols_ok = cols_ok && icols[c] >= 0 && icols[c] < t->shape[t->ndim];
@@ -2036,7 +1869,7 @@ int iso_interp_mag_host(iso_ic* ic, const double* pars, int64_t n, const int32_t
     if (n == 0) return ISO_OK;
     DeviceGuard guard(ic->device);
     std::lock_guard<std::mutex> lock(ic->ctx->stage_mu);
-    if (n == 1 && ic->g4.ncol <= 256 && service_enabled()) {
+    if (n == 1 && ic->g4.ncol <= 256 && resident_waves_enabled()) {
         // one point: the context's resident service wave (the generic column-parallel evaluation, which is also what a
         // one-point launch runs: no band pack is built for a small call)
         if (nb > 0 && !bc_cols) return fail(ISO_ERR_INVALID, "iso_interp_mag: bc_cols is NULL");
@@ -2087,7 +1920,7 @@ int iso_interp_eep_host(iso_eep_table* t, const double* age, const double* feh, 
     if (n == 0) return ISO_OK;
     DeviceGuard guard(t->device);
     std::lock_guard<std::mutex> lock(t->ctx->stage_mu);
-    if (n == 1 && service_enabled()) {
+    if (n == 1 && resident_waves_enabled()) {
         SvcTarget T;
         std::memset(&T, 0, sizeof T);
         T.op = ISO_SVC_EEP;
@@ -2454,10 +2287,6 @@ int iso_tree_model_create(iso_ic* ic, const iso_tree_desc* d, iso_tree_model** o
     m->d_bcq = nullptr;
     m->d_axes_blob = nullptr;
     m->fast_ok = false;
-    m->mbox = m->d_mbox = nullptr;
-    m->mbox_stream = nullptr;
-    m->mbox_count = 0;
-    m->mbox_state = 0;
     m->n_bands = d->n_bands;
     m->n_leaves = d->n_leaves;
     DevTree* H = new DevTree();
@@ -2549,56 +2378,10 @@ int iso_tree_model_create(iso_ic* ic, const iso_tree_desc* d, iso_tree_model** o
 }
 
 namespace {
-inline unsigned long long tmb_load(const volatile unsigned long long* p) { return __atomic_load_n(p, __ATOMIC_ACQUIRE); }
-
-bool tree_mailbox_launch(iso_tree_model* m)
-{
-    double idle_us = 1000.0;
-    if (const char* e = std::getenv("ISOCHRONES_AMD_MAILBOX_IDLE_US")) idle_us = std::max(10.0, std::atof(e));
-    const unsigned long long idle = (unsigned long long)(idle_us * 1e-6 * 1.0e8);       // wall_clock64(): 100 MHz
-    const unsigned long long life = (unsigned long long)(30.0 * 1.0e8);
-    __atomic_store_n(&m->mbox->ctl[1], 0ull, __ATOMIC_RELAXED);
-    __atomic_store_n(&m->mbox->ctl[0], 1ull, __ATOMIC_RELEASE);
-    FastArgs F = m->fast;
-    F.pars = nullptr;
-    F.n = 0;
-    F.lnpost = F.lnprior = F.lnlike = nullptr;
-    if (!launch_tree_mailbox(m->n_bands, m->n_leaves, F, m->d_tree, m->d_mbox, idle, life, m->mbox_stream) ||
-        hipGetLastError() != hipSuccess) {
-        __atomic_store_n(&m->mbox->ctl[0], 2ull, __ATOMIC_RELEASE);
-        return false;
-    }
-    return true;
-}
-
-bool tree_mailbox_ready(iso_tree_model* m)
-{
-    if (m->mbox_state < 0) return false;
-    if (m->mbox_state > 0) return true;
-    m->mbox_state = -1;
-    if (!m->fast_ok || m->n_params > 24) return false;
-    if (hipHostMalloc(reinterpret_cast<void**>(&m->mbox), sizeof(IsoTreeBox), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-        (void)hipGetLastError();
-        m->mbox = nullptr;
-        return false;
-    }
-    std::memset(m->mbox, 0, sizeof(IsoTreeBox));
-    m->mbox->ctl[0] = 2;                             // no wave yet
-    if (hipHostGetDevicePointer(reinterpret_cast<void**>(&m->d_mbox), m->mbox, 0) != hipSuccess ||
-        hipStreamCreateWithFlags(&m->mbox_stream, hipStreamNonBlocking) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipHostFree(m->mbox);
-        m->mbox = nullptr;
-        return false;
-    }
-    m->mbox_state = 1;
-    return true;
-}
-
 // one row through the resident wave; ISO_OK, or 1 = not served (the caller launches instead)
 int tree_mailbox_call(iso_tree_model* m, const double* pars, double* lnpost_out, double* lnprior_out, double* lnlike_out)
 {
-    IsoTreeBox* mb = m->mbox;
+    IsoTreeBox* mb = m->mbox.box;
     const int np_ = m->n_params;
     const bool parts = lnprior_out || lnlike_out;
     unsigned long long words[24];
@@ -2606,26 +2389,16 @@ int tree_mailbox_call(iso_tree_model* m, const double* pars, double* lnpost_out,
         std::memcpy(&words[q], pars + q, 8);
         __atomic_store_n(&mb->req[1 + q], words[q], __ATOMIC_RELAXED);
     }
-    const unsigned long long seq = ((unsigned long long)mailbox_checksum(words, np_) << 32) | ((++m->mbox_count & 0xFFFFull) << 16) |
+    const unsigned long long seq = ((unsigned long long)mailbox_checksum(words, np_) << 32) | ((++m->mbox.count & 0xFFFFull) << 16) |
                                    ((unsigned long long)parts << 8);
-    __atomic_store_n(&mb->req[0], seq, __ATOMIC_RELEASE);        // the sequence word last
-    if (tmb_load(&mb->ctl[0]) != 1 && !tree_mailbox_launch(m)) {
-        m->mbox_state = -1;                                      // no instantiation for this shape: the launch path from now on
-        return 1;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    for (uint64_t spins = 1; tmb_load(&mb->done[0]) != seq; ++spins) {
-        if ((spins & 255) == 0) {
-            if (tmb_load(&mb->ctl[0]) == 2 && tmb_load(&mb->done[0]) != seq) {
-                if (!tree_mailbox_launch(m)) return 1;
-            } else if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-                __atomic_store_n(&mb->ctl[1], 1ull, __ATOMIC_RELEASE);
-                (void)hipStreamSynchronize(m->mbox_stream);
-                m->mbox_state = -1;
-                return 1;
-            }
-        }
-    }
+    const bool served = m->mbox.call(seq, [m](IsoTreeBox* d_mb, unsigned long long idle, unsigned long long life, hipStream_t s) {
+        FastArgs F = m->fast;
+        F.pars = nullptr;
+        F.n = 0;
+        F.lnpost = F.lnprior = F.lnlike = nullptr;
+        return launch_tree_mailbox(m->n_bands, m->n_leaves, F, m->d_tree, d_mb, idle, life, s);
+    });
+    if (!served) return 1;
     double r[3];
     for (int k = 0; k < 3; ++k) {
         const unsigned long long w = __atomic_load_n(&mb->done[1 + k], __ATOMIC_RELAXED);
@@ -2634,43 +2407,23 @@ int tree_mailbox_call(iso_tree_model* m, const double* pars, double* lnpost_out,
     if (lnpost_out) *lnpost_out = r[0];
     if (lnprior_out) *lnprior_out = r[1];
     if (lnlike_out) *lnlike_out = r[2];
-#ifdef ISO_MAILBOX_CLOCK        // (variant builds: the wave's own time from seeing a request to its results, 100 MHz ticks)
+#ifdef ISO_MAILBOX_CLOCK
     {
-        static unsigned long long calls = 0, ticks = 0, ph[5] = {0, 0, 0, 0, 0};
-        ticks += __atomic_load_n(&mb->done[4], __ATOMIC_RELAXED);
+        static unsigned long long ph[5] = {0, 0, 0, 0, 0};
 #ifdef ISO_PHASE_CLOCK
         for (int k = 0; k < 3; ++k) ph[k] += __atomic_load_n(&mb->done[5 + k], __ATOMIC_RELAXED);
         for (int k = 0; k < 2; ++k) ph[3 + k] += __atomic_load_n(&mb->ctl[4 + k], __ATOMIC_RELAXED);
 #endif
-        if (++calls % 2000 == 0) {
-            std::fprintf(stderr, "tree mailbox: %.2f us on the device per call (%llu calls)\n", ticks * 0.01 / (double)calls, calls);
+        if (const unsigned long long calls = m->mbox.clock("tree mailbox")) {
 #ifdef ISO_PHASE_CLOCK
             std::fprintf(stderr, "tree mailbox: shader clocks from the request: first model cell %.0f, leaves done %.0f, priors %.0f, likelihood %.0f, results written %.0f\n",
                          ph[0] / (double)calls, ph[1] / (double)calls, ph[2] / (double)calls, ph[3] / (double)calls, ph[4] / (double)calls);
-            for (auto& v : ph) v = 0;
 #endif
-            calls = ticks = 0;
+            for (auto& v : ph) v = 0;
         }
     }
 #endif
     return ISO_OK;
-}
-
-void tree_mailbox_stop(iso_tree_model* m, bool release)
-{
-    if (!m->mbox) return;
-    if (tmb_load(&m->mbox->ctl[0]) == 1) {
-        __atomic_store_n(&m->mbox->ctl[1], 1ull, __ATOMIC_RELEASE);
-        (void)hipStreamSynchronize(m->mbox_stream);
-    }
-    if (release) {
-        (void)hipStreamSynchronize(m->mbox_stream);
-        (void)hipStreamDestroy(m->mbox_stream);
-        (void)hipHostFree(m->mbox);
-        m->mbox = m->d_mbox = nullptr;
-        m->mbox_stream = nullptr;
-        m->mbox_state = 0;
-    }
 }
 }  // namespace
 
@@ -2678,7 +2431,7 @@ void iso_tree_model_destroy(iso_tree_model* m)
 {
     if (!m) return;
     DeviceGuard guard(m->device);
-    tree_mailbox_stop(m, true);        // the resident wave reads the tables below
+    m->mbox.stop(true);                // the resident wave reads the tables below
     if (m->d_tree) (void)hipFree(m->d_tree);
     if (m->d_bc_hot) (void)hipFree(m->d_bc_hot);
     if (m->d_bcq) (void)hipFree(m->d_bcq);
@@ -2745,7 +2498,7 @@ int iso_tree_lnpost_host(iso_tree_model* m, const double* pars, int64_t n, doubl
     iso_ctx* ctx = m->ic->ctx;
     std::lock_guard<std::mutex> lock(ctx->stage_mu);
     // a sampler's per-point callback: the model's resident mailbox wave - no launch (fast/tree_mailbox.h)
-    if (n == 1 && mailbox_enabled() && tree_mailbox_ready(m)) {
+    if (n == 1 && resident_waves_enabled() && m->mbox.ready([m] { return m->fast_ok && m->n_params <= 24; })) {
         const int rc1 = tree_mailbox_call(m, pars, lnpost_out, lnprior_out, lnlike_out);
         if (rc1 <= 0) return rc1;
     }

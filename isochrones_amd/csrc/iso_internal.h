@@ -13,6 +13,7 @@
 #include <thread>
 
 #include "../../include/isochrones_amd.h"
+#include "fast/resident_wave.h"
 
 namespace iso {
 
@@ -202,31 +203,19 @@ struct AnyStretchArgs {
     double* chain_lnp;    // optional [nsteps][n_ens * W]
 };
 
-// the per-point callback's mailbox (iso_fast_mailbox.hip): pinned host memory, device-mapped, 64-byte lines
+// the per-point callback's mailbox (iso_fast_mailbox.hip; protocol: fast/resident_wave.h): pinned host memory, device-mapped,
+// 64-byte lines
 constexpr int ISO_MAILBOX_ROWS = 128;
 struct IsoMailbox {
     unsigned long long req[8];        // line 0, host -> device: req[0] = sequence word (checksum << 32 | counter << 16 | parts << 8 | rows - 1;
-                                      //         checksum = mailbox_checksum of the words of a one-row request, so that a line
-                                      //         whose eight words did not arrive together is seen as such and polled again),
+                                      //         checksum = mailbox_checksum of the words of a one-row request),
                                       //         req[1..7] = the parameters of a one-row request
     unsigned long long done[8];       // line 1, device -> host: done[0] = sequence word of the last finished request,
                                       //         done[1..3] = lnpost, lnprior, lnlike of a one-row request
-    unsigned long long ctl[8];        // line 2: ctl[0] = state (0 none, 1 running, 2 exited; the device writes 2),
-                                      //         ctl[1] = quit (host -> device)
+    unsigned long long ctl[8];        // line 2: ctl[0] = state, ctl[1] = quit
     double rows[ISO_MAILBOX_ROWS * ISO_MAX_PARAMS];     // requests of 2..128 rows, [row][parameter]
     double out[3 * ISO_MAILBOX_ROWS];                   // their results: lnpost | lnprior | lnlike
 };
-
-// 32-bit checksum of the parameter words of a one-row mailbox request (host and device compute the same number)
-__host__ __device__ inline uint32_t mailbox_checksum(const unsigned long long* w, int n)
-{
-    uint32_t c = 0x9E3779B9u;
-    for (int q = 0; q < n; ++q) {
-        c = (c ^ (uint32_t)w[q]) * 0x85EBCA6Bu;
-        c = (c ^ (uint32_t)(w[q] >> 32)) * 0xC2B2AE35u + (uint32_t)q;
-    }
-    return c;
-}
 
 // closed-form age prior of an IsoTrackModel (the reference's AgePrior, flat in linear age): lnorm + age ln 10 inside [lo, hi]
 struct IsoTrackAge {
@@ -341,12 +330,7 @@ struct iso_model {
     int64_t pipe_rows;
     hipStream_t pipe_stream[2];
     std::mutex host_mu;      // iso_lnpost_host: one caller at a time per model (the staging areas are the model's)
-    // resident mailbox wave of the per-point callback (lazy; guarded by host_mu)
-    iso::IsoMailbox* mbox;   // pinned, device-mapped
-    iso::IsoMailbox* d_mbox; // its device address
-    hipStream_t mbox_stream; // non-blocking: the resident wave must not order itself against the null stream
-    unsigned long long mbox_count;   // requests posted
-    int mbox_state;          // 0 untried, 1 usable, -1 not available for this model (no instantiation / allocation failed)
+    iso::ResidentWave<iso::IsoMailbox> mbox;   // the per-point callback's resident wave (lazy; guarded by host_mu)
 };
 
 struct iso_sampler {

@@ -15,7 +15,7 @@
 //               band numbers; req[0] = seq             -->  lanes 0-7 read the request line (one 64-B read over PCIe per poll); the
 //   (9-32 columns: req[8..10] behind the line)               sequence word carries the opcode, the column count and a 32-bit checksum
 //                                                            of the other words - a request whose words did not arrive together is
-//                                                            polled again (iso_internal.h: mailbox_checksum)
+//                                                            polled again (fast/resident_wave.h: the protocol)
 //                                                            the target's axes are staged in LDS when the target changes (a
 //                                                            target's record is only freed after the wave was told to leave, so
 //                                                            its address names it)
@@ -44,38 +44,26 @@ struct IsoSvcBox {
                                   // pointer), [2..6] coordinates / parameters, [7] column numbers 0-7 (a byte each); [8..10]
                                   // column numbers 8-31 of a request with more than eight
     unsigned long long done[8];   // [0] sequence word of the last finished request
-    unsigned long long ctl[8];    // [0] state (0 none, 1 running, 2 exited), [1] quit
+    unsigned long long ctl[8];    // [0] state, [1] quit
     double out[8 + ISO_SVC_MAX_COLS];
 };
 
-__device__ __forceinline__ unsigned long long svc_load(const unsigned long long* p)
-{
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ __forceinline__ void svc_store(unsigned long long* p, unsigned long long v)
-{
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 __device__ __forceinline__ void svc_out(double* p, double v)
 {
-    svc_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v));
+    sys_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v));
 }
 
 __global__ __launch_bounds__(64, 1) void k_service(IsoSvcBox* mb, unsigned long long idle_ticks, unsigned long long life_ticks)
 {
     extern __shared__ double lds[];
     const int lane = (int)threadIdx.x;
-    unsigned long long last = svc_load(&mb->done[0]);
+    WaveLoop<IsoSvcBox> W(mb, idle_ticks, life_ticks);
     unsigned long long staged = 0;                              // the target whose axes are in LDS
-    const unsigned long long t_start = wall_clock64();
-    unsigned long long t_idle = t_start;
     for (;;) {
-        const unsigned long long w = svc_load(&mb->req[lane & 7]);
+        const unsigned long long w = sys_load(&mb->req[lane & 7]);
         const unsigned long long seq = __shfl(w, 0);
-        if (seq == last) {
-            const unsigned long long now = wall_clock64();
-            const bool leave = (now - t_idle > idle_ticks) | (now - t_start > life_ticks) | (svc_load(&mb->ctl[1]) != 0);
-            if (leave) break;                                  // (wave-uniform)
+        if (seq == W.last) {
+            if (W.leave()) break;
             continue;
         }
         const int op = (int)(seq & 0xFF), k = (int)((seq >> 8) & 0xFF);
@@ -84,7 +72,7 @@ __global__ __launch_bounds__(64, 1) void k_service(IsoSvcBox* mb, unsigned long 
         for (int q = 0; q < 7; ++q) words[q] = __shfl(w, 1 + q);
         words[7] = words[8] = words[9] = 0;
         if (k > 8) {                                           // (wave-uniform) the column numbers behind the line
-            const unsigned long long w2 = svc_load(&mb->req[8 + (lane & 3)]);
+            const unsigned long long w2 = sys_load(&mb->req[8 + (lane & 3)]);
 #pragma unroll
             for (int q = 0; q < 3; ++q) words[7 + q] = __shfl(w2, q);
         }
@@ -156,11 +144,7 @@ __global__ __launch_bounds__(64, 1) void k_service(IsoSvcBox* mb, unsigned long 
             }
             if (lane == 0) svc_out(&mb->out[0], interp_eep_blend(T->E, c, ie, len));
         }
-        __threadfence_system();                                // results before the sequence word
-        if (lane == 0) svc_store(&mb->done[0], seq);
-        last = seq;
-        t_idle = wall_clock64();
+        W.answered(seq, lane);
     }
-    __threadfence_system();
-    if (lane == 0) svc_store(&mb->ctl[0], 2ull);              // state: exited
+    W.exit(lane);
 }
