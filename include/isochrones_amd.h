@@ -36,6 +36,7 @@
 #ifndef ISOCHRONES_AMD_H
 #define ISOCHRONES_AMD_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -315,6 +316,13 @@ int  iso_catalog_start_points(iso_catalog* c, int nwalkers, int oversample, int 
  * try / except around its fit, isochrones/starfit.py:155-159).  pos [S][nwalkers][n_params], lnp [S][nwalkers], failed [S]: DEVICE
  * arrays as iso_catalog_start_points wrote them.  With no good star at all the positions stay NaN. */
 int  iso_catalog_patch_failed(iso_catalog* c, int nwalkers, double* pos, double* lnp, const int32_t* failed, void* stream);
+
+/* The catalog's kernel-argument block (tables, staged axes, per-star blocks, shared-prior flag), copied to `out` for a
+ * companion library that launches its own kernels on the catalog (libiso_nested.so, include/isochrones_amd_nested.h).  Host
+ * only: nothing is launched.  `size` must be the size of that block in the caller's build - ISO_ERR_INVALID otherwise (a
+ * stale library) or when the catalog is not on the corner-packed path.  kind / n_stars_per_system / n_bands (each may be
+ * NULL) receive the catalog's shape.  The block holds device pointers the catalog owns: it is valid while the catalog is. */
+int  iso_catalog_fast_args(iso_catalog* c, void* out, size_t size, int* kind, int* n_stars_per_system, int* n_bands);
 
 /* Generic (observation-tree) StarModel: lnpost / lnprior / lnlike of starmodel.py:538-613 +
  * observation.py:1181-1234.  Outputs as iso_lnpost; lnlike is -inf (never NaN) when not finite,

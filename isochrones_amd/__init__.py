@@ -12,7 +12,8 @@ from .observation import ObservationTree, Observation, Source
 from ._cabi import IsoError
 from .sampler import EnsembleSampler, FusedEnsembleSampler
 from .catalog import (StarCatalog, CatalogPosterior, fit_catalog, synthetic_catalog, shard_of, shard_indices,
-                      broadcast_interpolator)
+                      broadcast_interpolator, fit_stars_nested_gpu, nested_result_columns, nested_max_live,
+                      select_multiplicity)
 from . import priors, grids, ingest, mist, nested, ini, persist, utils
 from .starfit import starfit, batch_starfit
 from .cluster import StarClusterModel, simulate_cluster

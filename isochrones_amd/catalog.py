@@ -637,6 +637,171 @@ def fit_stars_gpu(catalog: StarCatalog, ic, indices, N=1, nwalkers=32, nburn=150
     return out
 
 
+NESTED_STATS = ("mean", "std")
+NESTED_TAIL = ("lnZ", "lnZ_err", "H", "ncall", "niter", "prior_fraction", "status", "ok")
+#: device memory the dead points and the per-macro-step trace of ``return_dead=True`` may take; a larger request is refused
+NESTED_DEAD_BUDGET_BYTES = 2 << 30
+#: ``status`` of a nested row: 0 = fitted; 1 = fewer than n_live_points draws of the star's box had a finite posterior after
+#: max_fill_chunks chunks of 256 ("no support"); 2 = max_chunks chunks were drawn before the evidence converged
+NESTED_STATUS = {0: "ok", 1: "no support", 2: "call budget exhausted"}
+
+
+def nested_result_columns(param_names):
+    """Columns of a nested-sampling result row: posterior mean and standard deviation of every parameter, then the
+    evidence ``lnZ`` with its error, the information ``H``, the number of lnpost evaluations and of retired points, the
+    fraction of the prior box with a finite posterior, the status flag (``NESTED_STATUS``) and ``ok``."""
+    cols = []
+    for p in param_names:
+        cols += ["%s_%s" % (p, s) for s in NESTED_STATS]
+    return cols + list(NESTED_TAIL)
+
+
+def _catalog_param_names(ic, N):
+    return tuple(ic.param_names) if N == 1 else tuple(["eep_%d" % i for i in range(N)] + list(ic.param_names[1:]))
+
+
+def _nested_fast_args(post):
+    """The catalog's kernel-argument block for libiso_nested.so (an opaque byte buffer) and its shape."""
+    from . import _nested_cabi as NC
+    if not hasattr(_cabi.lib(), "iso_catalog_fast_args"):
+        raise _cabi.IsoError("isochrones_amd: libiso_hip.so does not export iso_catalog_fast_args - rebuild it")
+    size = int(NC.lib().iso_nested_fast_args_size())
+    buf = C.create_string_buffer(size)
+    kind, ns, nb = C.c_int(), C.c_int(), C.c_int()
+    _cabi.check(_cabi.lib().iso_catalog_fast_args(post._h, buf, size, C.byref(kind), C.byref(ns), C.byref(nb)))
+    return buf, size, kind.value, ns.value, nb.value
+
+
+def nested_max_live(catalog, ic, N=1, model_kwargs=None):
+    """The largest ``n_live_points`` :func:`fit_stars_nested_gpu` takes for this catalog's shape (stars per system, bands,
+    staged table axes): what fits the 160 KB of LDS one workgroup may hold."""
+    from . import _nested_cabi as NC
+    post = CatalogPosterior.from_catalog(catalog, ic, N=N, indices=np.arange(min(len(catalog), 1)), **(model_kwargs or {}))
+    try:
+        buf, size, _, ns, nb = _nested_fast_args(post)
+        return int(NC.lib().iso_nested_max_live_catalog(buf, size, ns, nb))
+    finally:
+        post.close()
+
+
+def fit_stars_nested_gpu(catalog: StarCatalog, ic, indices, N=1, n_live_points=400, evidence_tolerance=0.5, seed=0,
+                         max_iter=None, return_dead=False, model_kwargs=None, timings=None, enlarge=1.5,
+                         max_fill_chunks=4096, max_chunks=1 << 18):
+    """Nested-sampling fit of the stars ``indices`` of the catalog on the current GPU, all in ONE launch: one workgroup per
+    star, the live points in LDS ("Nested sampling of a catalog").  Returns [len(indices), 2 D + 8] float64 numpy
+    rows in :func:`nested_result_columns` order; a star that could not be fitted has ``ok = 0``, its ``status`` and NaN.
+
+    The prior is flat on each star's parameter box and ``loglike = lnpost``, as ``fit_multinest`` of a single model; a
+    star's random numbers are keyed by ``seed`` and its CATALOG ROW NUMBER (``indices``), so its row does not depend on
+    which other stars are fitted with it.  ``max_iter``: retired points per star at most (default 100 per live point).
+    ``return_dead=True``: also a dict with ``dead_u`` [S, max_dead, D] (unit cube), ``dead`` (parameters), ``logl``,
+    ``logwt`` (= logw + logl, not normalised) [S, max_dead], ``n_dead`` [S], the per-macro-step ``trace`` [S, max_steps,
+    3 + D + D D] (threshold, first draw examined, last draw consumed, ellipsoid mean and factor), ``n_steps`` [S], and
+    ``lo`` / ``hi`` [S, D] - numpy arrays."""
+    import torch
+    import time as _time
+    from . import _nested_cabi as NC
+
+    def _mark(name, _t=[_time.perf_counter()]):
+        if timings is not None:
+            torch.cuda.synchronize()
+            now = _time.perf_counter()
+            timings[name] = timings.get(name, 0.0) + now - _t[0]
+            _t[0] = now
+
+    indices = np.asarray(indices, dtype=np.int64)
+    D = N + 4
+    width = 2 * D + 8
+    n_live_points = int(n_live_points)
+    if n_live_points < max(20, 4 * (D + 1)):
+        raise ValueError("n_live_points must be at least max(20, 4 (D + 1)) = %d for the device-resident sampler"
+                         % max(20, 4 * (D + 1)))
+    n_bands = len([b for b in catalog.bands if b in ic.bc_grid.bands])
+    if n_bands > NC.MAX_BANDS:
+        raise NotImplementedError("the device-resident nested sampler covers 1-%d bands, this catalog has %d"
+                                  % (NC.MAX_BANDS, n_bands))
+    if indices.size == 0:
+        return (np.empty((0, width)), {}) if return_dead else np.empty((0, width))
+    post = CatalogPosterior.from_catalog(catalog, ic, N=N, indices=indices, **(model_kwargs or {}))
+    try:
+        if getattr(post.template, "_host_terms", None) is not None and post.template._host_terms():
+            raise NotImplementedError("priors evaluated on the host are not available inside the nested-sampling kernel")
+        if not (np.isfinite(post.bounds_lo).all() and np.isfinite(post.bounds_hi).all()):
+            raise ValueError("nested sampling needs a finite parameter box for every star (a prior without finite bounds?)")
+        buf, size, kind, ns, nb = _nested_fast_args(post)
+        L = NC.lib()
+        cap = int(L.iso_nested_max_live_catalog(buf, size, ns, nb))
+        if n_live_points > cap:
+            raise ValueError("n_live_points = %d is above the %d live points whose buffers fit a workgroup's LDS for %d "
+                             "star(s) per system and %d bands" % (n_live_points, cap, ns, nb))
+        _mark("build_posteriors")
+        S = post.n_models
+        K = int(L.iso_nested_remove(n_live_points, ns))
+        max_iter = int(100 * n_live_points if max_iter is None else max_iter)
+        device = torch.device("cuda", post.device)
+        gidx = torch.as_tensor(indices, dtype=torch.int64, device=device)
+        rows = torch.empty((S, width), dtype=torch.float64, device=device)
+        dead = n_dead = trace = n_steps = None
+        max_dead = max_steps = 0
+        if return_dead:
+            max_steps = (max_iter + K - 1) // K + 1
+            max_dead = max_steps * K + n_live_points
+            need = S * (max_dead * (D + 2) + max_steps * (3 + D + D * D)) * 8
+            if need > NESTED_DEAD_BUDGET_BYTES:
+                raise ValueError("return_dead: %d stars x %d dead points need %.1f GB of device memory (budget %.1f GB) - fit "
+                                 "fewer stars per call or lower max_iter" % (S, max_dead, need / 2**30,
+                                                                             NESTED_DEAD_BUDGET_BYTES / 2**30))
+            dead = torch.full((S, max_dead, D + 2), float("nan"), dtype=torch.float64, device=device)
+            trace = torch.full((S, max_steps, 3 + D + D * D), float("nan"), dtype=torch.float64, device=device)
+            n_dead = torch.zeros(S, dtype=torch.int32, device=device)
+            n_steps = torch.zeros(S, dtype=torch.int32, device=device)
+        opt = lambda t: dev.ptr(t) if t is not None else None
+        NC.check(L.iso_nested_fit(buf, size, kind, ns, nb, S, dev.ptr(gidx), n_live_points, float(evidence_tolerance),
+                                  float(enlarge), int(seed) & 0xFFFFFFFFFFFFFFFF, max_iter, int(max_fill_chunks), int(max_chunks),
+                                  dev.ptr(rows), opt(dead), opt(n_dead), max_dead, opt(trace), opt(n_steps), max_steps,
+                                  dev.stream_ptr(post.device)))
+        _mark("sampling")
+        out = rows.cpu().numpy()
+        extra = None
+        if return_dead:
+            d = dead.cpu().numpy()
+            lo, hi = post.bounds_lo.copy(), post.bounds_hi.copy()
+            extra = dict(dead_u=d[:, :, :D], dead=lo[:, None, :] + d[:, :, :D] * (hi - lo)[:, None, :], logl=d[:, :, D],
+                         logwt=d[:, :, D + 1], n_dead=n_dead.cpu().numpy(), trace=trace.cpu().numpy(),
+                         n_steps=n_steps.cpu().numpy(), lo=lo, hi=hi, K=K, kernel=L.iso_nested_last_kernel().decode())
+        _mark("summaries")
+    finally:
+        post.close()
+    return (out, extra) if return_dead else out
+
+
+def select_multiplicity(catalog: StarCatalog, ic, Ns=(1, 2), **fit_kwargs):
+    """Per-star model selection between multiplicities, what the reference's ``scripts/starmodel-select`` prints for one
+    star: the catalog is fitted by nested sampling once per ``N`` in ``Ns`` (``fit_catalog(..., method="nested")``, so the
+    sharding over ranks is the same) and the evidences are put side by side.  Returns a DataFrame indexed like the catalog:
+    ``lnZ_N``, ``lnZ_err_N`` per multiplicity, ``best_N`` (largest lnZ; 0 when no fit succeeded) and ``dlnZ`` = best minus
+    runner-up (NaN with fewer than two successful fits)."""
+    import pandas as pd
+    Ns = tuple(int(n) for n in Ns)
+    if len(Ns) < 1 or len(set(Ns)) != len(Ns):
+        raise ValueError("Ns must be distinct multiplicities")
+    cols = {}
+    for n in Ns:
+        res = fit_catalog(catalog, ic, N=n, method="nested", **fit_kwargs)
+        cols["lnZ_%d" % n] = res["lnZ"].to_numpy()
+        cols["lnZ_err_%d" % n] = res["lnZ_err"].to_numpy()
+    out = pd.DataFrame(cols, index=catalog.df.index)
+    z = np.column_stack([cols["lnZ_%d" % n] for n in Ns])
+    zf = np.where(np.isfinite(z), z, -np.inf)
+    have = np.isfinite(z).sum(axis=1)
+    best = np.argmax(zf, axis=1)
+    out["best_N"] = np.where(have > 0, np.asarray(Ns)[best], 0)
+    srt = np.sort(zf, axis=1)
+    with np.errstate(invalid="ignore"):
+        out["dlnZ"] = np.where(have > 1, srt[:, -1] - (srt[:, -2] if len(Ns) > 1 else np.nan), np.nan)
+    return out
+
+
 #: bump when the stored result rows change meaning (columns, summaries, sampler defaults)
 SHARD_FORMAT = 4
 
@@ -723,10 +888,14 @@ def _ic_signature(ic):
     return tuple(sig)
 
 
-def fit_catalog(catalog: StarCatalog, ic, N=1, fit_fn=None, checkpoint_dir=None, strict=None, **fit_kwargs):
+def fit_catalog(catalog: StarCatalog, ic, N=1, fit_fn=None, checkpoint_dir=None, strict=None, method="mcmc", **fit_kwargs):
     """Shard the catalog over the ranks of the default process group (star i -> rank (i+1) % P),
     fit every shard with ``fit_fn`` (default: :func:`fit_stars_gpu`) and all-gather the per-star
     result rows.  Returns a DataFrame indexed like ``catalog.df`` on every rank.
+
+    ``method="mcmc"`` (default): ensemble MCMC, rows in :func:`result_columns` order.  ``method="nested"``: per-star nested
+    sampling with :func:`fit_stars_nested_gpu` - evidences and posterior moments, rows in :func:`nested_result_columns`
+    order; sharding, gather, checkpoints and failure isolation are the same.
 
     Failure isolation (runs with more than one rank): a rank whose shard cannot be fitted (an exception in ``fit_fn``)
     contributes NaN rows with ``ok = 0`` and still takes part in every collective, so the other ranks' stars are not lost
@@ -756,8 +925,19 @@ def fit_catalog(catalog: StarCatalog, ic, N=1, fit_fn=None, checkpoint_dir=None,
         strict = world == 1
     n = len(catalog)
     mine = shard_indices(n, rank, world)
-    fit_fn = fit_fn or fit_stars_gpu
-    width = 3 * (N + 4) + 3
+    if method not in ("mcmc", "nested"):
+        raise ValueError("method must be 'mcmc' or 'nested'")
+    nested = method == "nested"
+    if nested and fit_fn is not None:
+        raise ValueError("method='nested' brings its own fit function")
+    if nested and fit_kwargs.get("return_dead"):
+        raise ValueError("return_dead is fit_stars_nested_gpu's: fit_catalog gathers fixed-size rows only")
+    fit_fn = fit_fn or (fit_stars_nested_gpu if nested else fit_stars_gpu)
+    names = _catalog_param_names(ic, N)
+    columns = nested_result_columns(names) if nested else result_columns(names)
+    width = len(columns) if nested else 3 * (N + 4) + 3
+    # (the digest of an MCMC shard is what it was before there was a method; a nested shard's carries the method)
+    digest_kwargs = dict(fit_kwargs, method=method) if nested else fit_kwargs
     rows, ckpt, error = None, None, None
     phases = {}
     t_fit = _time.perf_counter()
@@ -768,7 +948,7 @@ def fit_catalog(catalog: StarCatalog, ic, N=1, fit_fn=None, checkpoint_dir=None,
         if checkpoint_dir is not None:
             os.makedirs(checkpoint_dir, exist_ok=True)
             ckpt = os.path.join(checkpoint_dir, "shard_%dof%d.npz" % (rank, world))
-            digest = _shard_fingerprint(catalog, mine, N, fit_kwargs, ic)
+            digest = _shard_fingerprint(catalog, mine, N, digest_kwargs, ic)
             if os.path.exists(ckpt):
                 try:
                     with np.load(ckpt, allow_pickle=False) as z:
@@ -778,7 +958,7 @@ def fit_catalog(catalog: StarCatalog, ic, N=1, fit_fn=None, checkpoint_dir=None,
                     rows = None
         if rows is None:
             kw = dict(fit_kwargs)
-            if fit_fn is fit_stars_gpu and "timings" not in kw:
+            if fit_fn in (fit_stars_gpu, fit_stars_nested_gpu) and "timings" not in kw:
                 kw["timings"] = phases           # where this rank's fit spends its time (attrs["timings"]["phases"])
             rows = np.asarray(fit_fn(catalog, ic, mine, N=N, **kw), dtype=np.float64)
             if rows.shape != (len(mine), width):
@@ -837,8 +1017,7 @@ def fit_catalog(catalog: StarCatalog, ic, N=1, fit_fn=None, checkpoint_dir=None,
         if strict:
             raise RuntimeError(msg)
         warnings.warn(msg, RuntimeWarning)
-    names = (ic.param_names if N == 1 else tuple(["eep_%d" % i for i in range(N)] + list(ic.param_names[1:])))
-    out = pd.DataFrame(full, index=catalog.df.index, columns=result_columns(names))
+    out = pd.DataFrame(full, index=catalog.df.index, columns=columns)
     out.attrs["shard_errors"] = errors
     out.attrs["timings"] = {"fit_s": t_gather - t_fit, "gather_s": t_end - t_gather, "world": world, "rank": rank,
                             "backend": dist.get_backend() if distributed else None, "stars_of_this_rank": int(len(mine)),

@@ -2239,6 +2239,20 @@ int iso_catalog_patch_failed(iso_catalog* c, int nwalkers, double* pos, double* 
     return ISO_OK;
 }
 
+int iso_catalog_fast_args(iso_catalog* c, void* out, size_t size, int* kind, int* n_stars_per_system, int* n_bands)
+{
+    if (!c || !out) return fail(ISO_ERR_INVALID, "iso_catalog_fast_args: NULL argument");
+    if (size != sizeof(FastArgs))
+        return fail(ISO_ERR_INVALID, "iso_catalog_fast_args: the caller's kernel-argument block has another size than this library's (stale build?)");
+    if (!c->packed || !c->fast.hotq || !c->fast.bcq || !c->fast.m)
+        return fail(ISO_ERR_INVALID, "iso_catalog_fast_args: the catalog is not on the corner-packed path");
+    std::memcpy(out, &c->fast, sizeof(FastArgs));
+    if (kind) *kind = c->ic->kind;
+    if (n_stars_per_system) *n_stars_per_system = c->n_stars;
+    if (n_bands) *n_bands = c->n_bands;
+    return ISO_OK;
+}
+
 int iso_tree_model_create(iso_ic* ic, const iso_tree_desc* d, iso_tree_model** out)
 {
     if (!ic || !d || !out) return fail(ISO_ERR_INVALID, "iso_tree_model_create: NULL argument");
