@@ -372,10 +372,11 @@ class StarClusterModel(_NestedFitMixin):
 
 
 def simulate_cluster(N, age, feh, distance, AV, alpha, gamma, fB, bands="JHK", mass_range=(0.8, 2.5),
-                     distance_scatter=5, ic=None, seed=None):
+                     distance_scatter=5, ic=None, seed=None, accurate=False):
     """A synthetic cluster catalog (reference: cluster.py:414-477), drawn with ``numpy.random.default_rng(seed)`` and
     batched ``get_eep`` / ``interp_mag`` calls.  A secondary below the table's mass range has a NaN EEP; a single star's
-    secondary magnitude is infinite, so its total is the primary's."""
+    secondary magnitude is infinite, so its total is the primary's.  ``accurate`` goes to both ``get_eep`` calls
+    (``"exact"``: the device solve of ``solve_eep``)."""
     import pandas as pd
     from .models import get_ichrone
     from .utils import addmags
@@ -388,8 +389,8 @@ def simulate_cluster(N, age, feh, distance, AV, alpha, gamma, fB, bands="JHK", m
     if ic is None:
         ic = get_ichrone("mist", bands=bands)
     ones = np.ones(N)
-    pri_eeps = np.asarray(ic.get_eep(pri_masses, age * ones, feh * ones), dtype=float).reshape(N)
-    sec_eeps = np.asarray(ic.get_eep(sec_masses, age * ones, feh * ones), dtype=float).reshape(N)
+    pri_eeps = np.asarray(ic.get_eep(pri_masses, age * ones, feh * ones, accurate=accurate), dtype=float).reshape(N)
+    sec_eeps = np.asarray(ic.get_eep(sec_masses, age * ones, feh * ones, accurate=accurate), dtype=float).reshape(N)
     distances = distance + rng.standard_normal(N) * distance_scatter
     _, _, _, mp = ic.interp_mag([pri_eeps, age * ones, feh * ones, distances, AV * ones], bands)
     _, _, _, ms = ic.interp_mag([sec_eeps, age * ones, feh * ones, distances, AV * ones], bands)

@@ -100,6 +100,18 @@ class _ScalarEEP:
         self.args = (handle, a, a + 8, a + 16, 1, a + 24)          # table, age, feh, mass, one point, eep
 
 
+def _wants_exact(accurate, args, kwargs):
+    """Whether a ``get_eep`` call goes to ``solve_eep``: ``accurate="exact"``, or ``accurate=True`` with CUDA tensors
+    (which the per-star optimiser cannot take)."""
+    if isinstance(accurate, str):
+        if accurate != "exact":
+            raise ValueError("accurate must be False, True or 'exact', not %r" % (accurate,))
+        if kwargs:
+            raise TypeError("get_eep(accurate='exact') takes no optimiser keywords (got %s)" % sorted(kwargs))
+        return True
+    return bool(accurate) and any(dev.is_tensor(a) and a.is_cuda for a in args)
+
+
 class ModelGridInterpolator:
     param_names = None
     eep_replaces = None
@@ -189,6 +201,7 @@ class ModelGridInterpolator:
     def release(self):
         self._handles.release()
         self._eep_handles.release()
+        self.__dict__.pop("_solve_tables", None)
 
     def __del__(self):
         try:
@@ -417,11 +430,72 @@ class ModelGridInterpolator:
             return np.nan
         raise RuntimeError("EEP minimization not successful: {}".format((mass, age, feh)))
 
+    # -- exact (mass, age, feh) -> EEP: one column inverted along the EEP axis by libiso_solve.so --------------------
+    def _solve_host(self):
+        """(column, ranges) of the column :meth:`solve_eep` inverts, checked once per table (rebuilt when the table is);
+        raises the ``ValueError`` of :func:`solve.column_ranges` for a table whose column decreases somewhere."""
+        from . import solve
+        dfi = self.model_grid.interp
+        gen = dfi._handles.generation
+        c = self.__dict__.get("_solve_host_cache")
+        if c is None or c[0] != gen:
+            name = "age" if self.eep_replaces == "age" else "initial_mass"
+            col = np.ascontiguousarray(dfi.grid[..., dfi.column_index[name]])
+            try:
+                c = (gen, col, solve.column_ranges(col, name))
+            except ValueError as e:
+                c = (gen, None, e)
+            self._solve_host_cache = c
+        if c[1] is None:
+            raise ValueError(str(c[2]))
+        return c[1], c[2]
+
+    def _solve_table(self, device):
+        """Device copies of the column, the axes and the ranges: made once per device, remade when the table was
+        rebuilt (the rule of ``_eep_handles``: compare the table's generation)."""
+        from . import solve
+        col, ranges = self._solve_host()
+        gen = self.model_grid.interp._handles.generation
+        tables = self.__dict__.setdefault("_solve_tables", {})
+        entry = tables.get(device)
+        if entry is None or entry[0] != gen:
+            entry = tables[device] = (gen, solve.DeviceTable(col, self.model_grid.interp.index_columns, ranges, device))
+        return entry[1]
+
+    def solve_eep(self, mass, age, feh):
+        """The EEP at which a star of given (mass, log10 age, feh) sits, exact to rounding: the interpolated ``age``
+        along (mass, feh) of a track table - ``initial_mass`` along (age, feh) of an isochrone table - is piecewise
+        linear and nondecreasing in EEP, so one kernel brackets the target between two EEP knots and inverts the
+        segment (include/isochrones_amd_solve.h has the definition).  Where several EEPs give the target (a plateau)
+        the smallest is returned; NaN where there is none, for NaN or off-table input and next to holes of the table -
+        never an exception per star.  Call forms as :meth:`get_eep`: scalars -> float, arrays (broadcast) -> numpy,
+        CUDA tensors -> CUDA tensor on the same device, on the current stream, without a host round trip.  A table
+        whose column decreases somewhere along EEP raises ``ValueError``."""
+        self._solve_host()                              # refuses a table before any device is asked for
+        # (x0, x1, target) in the order of the table's axes
+        args = [feh, mass, age] if self.eep_replaces == "age" else [age, feh, mass]
+        if any(dev.is_tensor(a) and a.is_cuda for a in args):
+            import torch
+            device = next(a.device.index for a in args if dev.is_tensor(a) and a.is_cuda)
+            xs = [t.reshape(-1).contiguous() for t in
+                  torch.broadcast_tensors(*[dev.to_device_f64(x, device) for x in args])]
+            return self._solve_table(device).solve_device(*xs)
+        table = self._solve_table(dev.current_device())
+        scalar = all(isinstance(x, (float, int, np.floating, np.integer)) for x in args)
+        xs = [np.ascontiguousarray(x, dtype=float).ravel() for x in np.broadcast_arrays(*args)]
+        res = table.solve_host(*xs)
+        return float(res[0]) if scalar else res
+
     def get_eep(self, mass, age, feh, accurate=False, **kwargs):
         """EEP of a star of given (mass, log10 age, feh): bilinear blend over the four neighbouring
         tracks of the first EEP whose age exceeds ``age`` (reference ``interp_eep(s)``).  Scalars
         -> float, arrays -> numpy, CUDA tensors -> CUDA tensor.  ``accurate=True`` refines a scalar
-        result with :meth:`get_eep_accurate` starting from the fast estimate, as the reference."""
+        result with :meth:`get_eep_accurate` starting from the fast estimate, as the reference (one
+        Nelder-Mead per star for host arrays).  ``accurate="exact"`` is :meth:`solve_eep` in every
+        call form; CUDA tensors with ``accurate=True`` take it too (the optimiser's keywords have no
+        meaning there and are ignored)."""
+        if _wants_exact(accurate, (mass, age, feh), kwargs):
+            return self.solve_eep(mass, age, feh)
         if accurate:
             eep0 = self.get_eep(mass, age, feh)
             if np.ndim(eep0) == 0:
@@ -589,6 +663,8 @@ class IsochroneInterpolator(ModelGridInterpolator):
     def get_eep(self, mass, age, feh, accurate=False, **kwargs):
         """Fast estimate from the companion track grid (reference: IsochroneInterpolator delegates to
         ``self.track``), optionally refined against this grid's own initial_mass column."""
+        if _wants_exact(accurate, (mass, age, feh), kwargs):
+            return self.solve_eep(mass, age, feh)        # on this grid's own initial_mass column
         eep0 = self.track.get_eep(mass, age, feh)
         if not accurate:
             return eep0
