@@ -17,5 +17,6 @@ from .catalog import (StarCatalog, CatalogPosterior, fit_catalog, synthetic_cata
 from . import priors, grids, ingest, mist, nested, ini, persist, utils
 from .starfit import starfit, batch_starfit
 from .cluster import StarClusterModel, simulate_cluster
+from .diagnostics import chain_diagnostics, ChainDiagnostics
 
 __version__ = "0.1.0"

@@ -507,18 +507,32 @@ def initial_positions(post: CatalogPosterior, nwalkers, rng_seed=0, oversample=8
 RESULT_STATS = ("median", "p16", "p84")
 
 
-def result_columns(param_names):
+DIAG_STATS = ("tau", "ess", "rhat")
+DIAG_TAIL = ("tau_max", "rhat_max", "window_ok")
+
+
+def result_columns(param_names, diagnostics=False):
+    """Columns of an MCMC result row.  ``diagnostics=True`` adds, between ``acceptance`` and ``ok`` (which stays last), the
+    per-parameter ``{p}_tau, {p}_ess, {p}_rhat`` and the per-star ``tau_max``, ``rhat_max`` and ``window_ok`` (the minimum
+    over the parameters: 1 only where every parameter's autocorrelation window was found)."""
     cols = []
     for p in param_names:
         cols += ["%s_%s" % (p, s) for s in RESULT_STATS]
-    return cols + ["lnpost_max", "acceptance", "ok"]
+    cols += ["lnpost_max", "acceptance"]
+    if diagnostics:
+        for p in param_names:
+            cols += ["%s_%s" % (p, s) for s in DIAG_STATS]
+        cols += list(DIAG_TAIL)
+    return cols + ["ok"]
 
 
 def fit_stars_gpu(catalog: StarCatalog, ic, indices, N=1, nwalkers=32, nburn=150, niter=100, seed=0,
                   model_kwargs=None, fused=True, timings=None, max_stars_per_batch=200_000, return_chains=False,
-                  replay_record=None):
+                  replay_record=None, diagnostics=False):
     """Fit the stars ``indices`` of the catalog on the current GPU; returns [len(indices), 3*D+3]
-    float64 numpy rows (result_columns order).  ``return_chains=True`` (fused sampler, one batch): also the
+    float64 numpy rows (result_columns order).  ``diagnostics=True`` (fused sampler): 3*D+3 more columns, the stored
+    chain's per-parameter autocorrelation time, effective sample size and split R-hat and their per-star summary
+    (``result_columns(names, diagnostics=True)``; one launch of the libiso_diag.so kernel on the chain where it lies).  ``return_chains=True`` (fused sampler, one batch): also the
     stored chain [S, W, niter, D] and its lnpost values [S, W, niter] as CUDA tensors.  ``replay_record`` (a dict, tests):
     filled with what a move-by-move replay of the SAMPLING run needs - the ensembles as burn-in left them (``pos`` [S, W, D],
     ``lnp`` [S, W]), the sampler's ``seed``, the step counter the run starts at (``step0`` = nburn), the start points."""
@@ -532,15 +546,19 @@ def fit_stars_gpu(catalog: StarCatalog, ic, indices, N=1, nwalkers=32, nburn=150
             timings[name] = timings.get(name, 0.0) + now - _t[0]
             _t[0] = now
 
+    if diagnostics and not fused:
+        raise ValueError("diagnostics=True needs the fused sampler (its stored chain is what the diagnostics kernel reads)")
+    n_diag = 3 * (N + 4) + 3 if diagnostics else 0          # columns between acceptance and ok
     if len(indices) == 0:
-        return np.empty((0, 3 * (N + 4) + 3))
+        return np.empty((0, 3 * (N + 4) + 3 + n_diag))
     if return_chains and (not fused or len(indices) > max_stars_per_batch):
         raise ValueError("return_chains needs the fused sampler and at most max_stars_per_batch stars")
     if len(indices) > max_stars_per_batch:
         # bound the device memory of the stored chains (S x W x niter x D doubles): fit the shard in slices
         parts = [fit_stars_gpu(catalog, ic, indices[k:k + max_stars_per_batch], N=N, nwalkers=nwalkers, nburn=nburn,
                                niter=niter, seed=seed + 7919 * (k // max_stars_per_batch), model_kwargs=model_kwargs,
-                               fused=fused, timings=timings, max_stars_per_batch=max_stars_per_batch)
+                               fused=fused, timings=timings, max_stars_per_batch=max_stars_per_batch,
+                               diagnostics=diagnostics)
                  for k in range(0, len(indices), max_stars_per_batch)]
         return np.concatenate(parts, axis=0)
     post = CatalogPosterior.from_catalog(catalog, ic, N=N, indices=indices, **(model_kwargs or {}))
@@ -562,8 +580,8 @@ def fit_stars_gpu(catalog: StarCatalog, ic, indices, N=1, nwalkers=32, nburn=150
         if not bool(good.any()):
             # no star of the batch found a start point: nothing to sample, every row reports ok = 0
             post.close()
-            out = np.full((post.n_models, 3 * D + 3), np.nan)
-            out[:, 3 * D + 2] = 0.0
+            out = np.full((post.n_models, 3 * D + 3 + n_diag), np.nan)
+            out[:, -1] = 0.0
             if return_chains:
                 raise ValueError("no star of the batch has a start point with a finite lnpost")
             return out
@@ -587,6 +605,9 @@ def fit_stars_gpu(catalog: StarCatalog, ic, indices, N=1, nwalkers=32, nburn=150
         sampler.reset()
         sampler.run_mcmc(pos, niter, lnprob0=lnp, store=True, check=not lean, inplace=lean)
         _mark("sampling")
+        if diagnostics:
+            dg = sampler.diagnostics()                              # [S, D] each, from the parameter-major storage
+            _mark("diagnostics")
         chain, lnps = sampler.chain, sampler.lnprobability        # [S, W, niter, D], [S, W, niter]
         acc_frac = sampler.acceptance_fraction.mean(dim=1)
     else:
@@ -615,19 +636,25 @@ def fit_stars_gpu(catalog: StarCatalog, ic, indices, N=1, nwalkers=32, nburn=150
         i1 = torch.clamp(i0 + 1, max=m - 1)
         frac = pick - i0.to(torch.float64)
         q = srt[:, :, i0] * (1 - frac) + srt[:, :, i1] * frac                                   # [S, D, 3] (linear, as np.percentile)
-    rows = torch.empty(post.n_models, 3 * D + 3, dtype=torch.float64, device=q.device)
+    rows = torch.empty(post.n_models, 3 * D + 3 + n_diag, dtype=torch.float64, device=q.device)
     rows[:, : 3 * D] = q.reshape(post.n_models, 3 * D)
     if fused:       # storage order is [step][star * W + walker]: reduce over steps first (coalesced), then walkers
         rows[:, 3 * D] = sampler._lnprob.amax(dim=0).view(post.n_models, nwalkers).amax(dim=1)
     else:
         rows[:, 3 * D] = lnps.amax(dim=(1, 2))
     rows[:, 3 * D + 1] = acc_frac
-    rows[:, 3 * D + 2] = good.to(torch.float64)
-    rows[failed, : 3 * D + 2] = float("nan")
+    if diagnostics:
+        d0 = 3 * D + 2
+        rows[:, d0: d0 + 3 * D] = torch.stack([dg.tau, dg.ess, dg.rhat], dim=2).reshape(post.n_models, 3 * D)
+        rows[:, d0 + 3 * D] = dg.tau.amax(dim=1)
+        rows[:, d0 + 3 * D + 1] = dg.rhat.amax(dim=1)
+        rows[:, d0 + 3 * D + 2] = dg.window_ok.amin(dim=1)
+    rows[:, -1] = good.to(torch.float64)
+    rows[failed, :-1] = float("nan")
     out = rows.cpu().numpy()
     _mark("summaries")
     if return_chains:
-        if not out[:, 3 * D + 2].any():
+        if not out[:, -1].any():
             post.close()
             raise ValueError("no star of the batch has a start point with a finite lnpost")
         kept = (chain.clone(), lnps.clone())
@@ -934,8 +961,14 @@ def fit_catalog(catalog: StarCatalog, ic, N=1, fit_fn=None, checkpoint_dir=None,
         raise ValueError("return_dead is fit_stars_nested_gpu's: fit_catalog gathers fixed-size rows only")
     fit_fn = fit_fn or (fit_stars_nested_gpu if nested else fit_stars_gpu)
     names = _catalog_param_names(ic, N)
-    columns = nested_result_columns(names) if nested else result_columns(names)
-    width = len(columns) if nested else 3 * (N + 4) + 3
+    diagnostics = bool(fit_kwargs.get("diagnostics", False))
+    if nested and diagnostics:
+        raise ValueError("diagnostics=True is for method='mcmc': a nested run stores no chain")
+    if not diagnostics:
+        # an explicit False is the default: the same call, the same rows, the same checkpoint digest
+        fit_kwargs = {k: v for k, v in fit_kwargs.items() if k != "diagnostics"}
+    columns = nested_result_columns(names) if nested else result_columns(names, diagnostics=diagnostics)
+    width = len(columns)
     # (the digest of an MCMC shard is what it was before there was a method; a nested shard's carries the method)
     digest_kwargs = dict(fit_kwargs, method=method) if nested else fit_kwargs
     rows, ckpt, error = None, None, None
@@ -1019,12 +1052,16 @@ def fit_catalog(catalog: StarCatalog, ic, N=1, fit_fn=None, checkpoint_dir=None,
         warnings.warn(msg, RuntimeWarning)
     out = pd.DataFrame(full, index=catalog.df.index, columns=columns)
     out.attrs["shard_errors"] = errors
+    if diagnostics:
+        phases_extra = {"diag_s": phases.get("diagnostics", 0.0)}      # the diagnostics launch, apart from summary_s
+    else:
+        phases_extra = {}
     out.attrs["timings"] = {"fit_s": t_gather - t_fit, "gather_s": t_end - t_gather, "world": world, "rank": rank,
                             "backend": dist.get_backend() if distributed else None, "stars_of_this_rank": int(len(mine)),
                             # this rank's shard by phase: per-star blocks, start points, burn-in + sampling, summaries (+ D2H)
                             "phases": {"build_s": phases.get("build_posteriors", 0.0), "start_s": phases.get("initial_positions", 0.0),
                                        "sample_s": phases.get("burn_in", 0.0) + phases.get("sampling", 0.0),
-                                       "summary_s": phases.get("summaries", 0.0)}}
+                                       "summary_s": phases.get("summaries", 0.0), **phases_extra}}
     return out
 
 

@@ -306,6 +306,31 @@ class FusedEnsembleSampler:
         """results carry a leading ensemble axis: catalogs (one ensemble per star) and multi-ensemble model samplers"""
         return self.is_catalog or self.multi_ensemble
 
+    def diagnostics(self, c=5.0, max_lag=1024):
+        """Convergence diagnostics of the stored chain per (ensemble, parameter): a
+        :class:`isochrones_amd.diagnostics.ChainDiagnostics` of [S, ndim] (model: [ndim]) CUDA tensors - ``tau`` (integrated
+        autocorrelation time, Sokal's window ``c``), ``window``, ``window_ok``, ``ess`` and split ``rhat``.  One launch of
+        ``iso_diag_chain`` on the parameter-major storage, no copy; a model sampler and a catalog sampler alike."""
+        from . import _diag_cabi, diagnostics as dg
+        if self._chain is None:
+            raise ValueError("no stored chain")
+        out = dg.diag_storage(self._chain, self.n_ensembles, self.nwalkers, c, max_lag)
+        if not self._stacked:
+            out = out[0]
+        return dg.ChainDiagnostics(*(out[..., i] for i in range(_diag_cabi.NOUT)))
+
+    def get_autocorr_time(self, c=5.0, max_lag=1024):
+        """Integrated autocorrelation time per parameter in steps (named as emcee names it), [S, ndim] or [ndim]."""
+        return self.diagnostics(c, max_lag).tau
+
+    def effective_sample_size(self, c=5.0, max_lag=1024):
+        """W T / tau per parameter."""
+        return self.diagnostics(c, max_lag).ess
+
+    def split_rhat(self):
+        """Split R-hat per parameter over the 2 W half-chains of each ensemble's walkers."""
+        return self.diagnostics().rhat
+
     def gelman_rubin(self):
         """Potential scale reduction factor R-hat per parameter across the independent ensembles of a multi-ensemble
         model sampler (Gelman & Rubin 1992: between- vs within-chain variance of the ensemble means; each ensemble's
