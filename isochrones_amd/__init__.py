@@ -18,5 +18,6 @@ from . import priors, grids, ingest, mist, nested, ini, persist, utils
 from .starfit import starfit, batch_starfit
 from .cluster import StarClusterModel, simulate_cluster
 from .diagnostics import chain_diagnostics, ChainDiagnostics
+from .derived import chain_derived
 
 __version__ = "0.1.0"

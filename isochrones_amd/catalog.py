@@ -511,10 +511,12 @@ DIAG_STATS = ("tau", "ess", "rhat")
 DIAG_TAIL = ("tau_max", "rhat_max", "window_ok")
 
 
-def result_columns(param_names, diagnostics=False):
+def result_columns(param_names, diagnostics=False, derived=()):
     """Columns of an MCMC result row.  ``diagnostics=True`` adds, between ``acceptance`` and ``ok`` (which stays last), the
     per-parameter ``{p}_tau, {p}_ess, {p}_rhat`` and the per-star ``tau_max``, ``rhat_max`` and ``window_ok`` (the minimum
-    over the parameters: 1 only where every parameter's autocorrelation window was found)."""
+    over the parameters: 1 only where every parameter's autocorrelation window was found).  ``derived``: the labels of
+    derived properties, already expanded (``{label}_{k}`` for N > 1, :func:`isochrones_amd.derived.expand_labels`); each adds
+    ``{label}_median, _p16, _p84`` after the diagnostics columns and before ``ok``."""
     cols = []
     for p in param_names:
         cols += ["%s_%s" % (p, s) for s in RESULT_STATS]
@@ -523,16 +525,34 @@ def result_columns(param_names, diagnostics=False):
         for p in param_names:
             cols += ["%s_%s" % (p, s) for s in DIAG_STATS]
         cols += list(DIAG_TAIL)
+    for label in derived:
+        cols += ["%s_%s" % (label, s) for s in RESULT_STATS]
     return cols + ["ok"]
+
+
+def _derived_request(ic, derived, N):
+    """``derived`` of fit_stars_gpu / fit_catalog -> (props, expanded labels): None / False / () -> ((), ()); True -> the
+    default properties of the grid (:func:`isochrones_amd.derived.default_props`); a sequence of column names or
+    ``(label, column)`` pairs is checked against the grid and the fit's parameter names."""
+    from . import derived as dv
+    if derived is None or derived is False or (not isinstance(derived, (bool, str)) and len(derived) == 0):
+        return (), ()
+    props = dv.default_props(ic, N) if derived is True else ((derived,) if isinstance(derived, str) else tuple(derived))
+    labels, _ = dv.resolve_props(ic, props, N)
+    return props, dv.expand_labels(labels, N)
 
 
 def fit_stars_gpu(catalog: StarCatalog, ic, indices, N=1, nwalkers=32, nburn=150, niter=100, seed=0,
                   model_kwargs=None, fused=True, timings=None, max_stars_per_batch=200_000, return_chains=False,
-                  replay_record=None, diagnostics=False):
+                  replay_record=None, diagnostics=False, derived=None):
     """Fit the stars ``indices`` of the catalog on the current GPU; returns [len(indices), 3*D+3]
     float64 numpy rows (result_columns order).  ``diagnostics=True`` (fused sampler): 3*D+3 more columns, the stored
     chain's per-parameter autocorrelation time, effective sample size and split R-hat and their per-star summary
-    (``result_columns(names, diagnostics=True)``; one launch of the libiso_diag.so kernel on the chain where it lies).  ``return_chains=True`` (fused sampler, one batch): also the
+    (``result_columns(names, diagnostics=True)``; one launch of the libiso_diag.so kernel on the chain where it lies).
+    ``derived`` (fused sampler): a sequence of model-grid column names or ``(label, column)`` pairs, or ``True`` for those of
+    mass, radius, age, Teff, logg the grid has and the fit does not sample; per label three more columns, the median, 16th
+    and 84th percentile of that property over the star's chain (the libiso_derived.so kernel on the chain where it lies,
+    then the quantile kernel), NaN where a sample of the star fell off the grid.  ``return_chains=True`` (fused sampler, one batch): also the
     stored chain [S, W, niter, D] and its lnpost values [S, W, niter] as CUDA tensors.  ``replay_record`` (a dict, tests):
     filled with what a move-by-move replay of the SAMPLING run needs - the ensembles as burn-in left them (``pos`` [S, W, D],
     ``lnp`` [S, W]), the sampler's ``seed``, the step counter the run starts at (``step0`` = nburn), the start points."""
@@ -548,7 +568,11 @@ def fit_stars_gpu(catalog: StarCatalog, ic, indices, N=1, nwalkers=32, nburn=150
 
     if diagnostics and not fused:
         raise ValueError("diagnostics=True needs the fused sampler (its stored chain is what the diagnostics kernel reads)")
+    derived_props, derived_labels = _derived_request(ic, derived, N)
+    if derived_props and not fused:
+        raise ValueError("derived needs the fused sampler (its stored chain is what the derived-properties kernel reads)")
     n_diag = 3 * (N + 4) + 3 if diagnostics else 0          # columns between acceptance and ok
+    n_diag += 3 * len(derived_labels)
     if len(indices) == 0:
         return np.empty((0, 3 * (N + 4) + 3 + n_diag))
     if return_chains and (not fused or len(indices) > max_stars_per_batch):
@@ -558,7 +582,7 @@ def fit_stars_gpu(catalog: StarCatalog, ic, indices, N=1, nwalkers=32, nburn=150
         parts = [fit_stars_gpu(catalog, ic, indices[k:k + max_stars_per_batch], N=N, nwalkers=nwalkers, nburn=nburn,
                                niter=niter, seed=seed + 7919 * (k // max_stars_per_batch), model_kwargs=model_kwargs,
                                fused=fused, timings=timings, max_stars_per_batch=max_stars_per_batch,
-                               diagnostics=diagnostics)
+                               diagnostics=diagnostics, derived=derived)
                  for k in range(0, len(indices), max_stars_per_batch)]
         return np.concatenate(parts, axis=0)
     post = CatalogPosterior.from_catalog(catalog, ic, N=N, indices=indices, **(model_kwargs or {}))
@@ -608,6 +632,9 @@ def fit_stars_gpu(catalog: StarCatalog, ic, indices, N=1, nwalkers=32, nburn=150
         if diagnostics:
             dg = sampler.diagnostics()                              # [S, D] each, from the parameter-major storage
             _mark("diagnostics")
+        if derived_props:
+            dq, dnan = sampler.derived_quantiles(ic, derived_props, (0.5, 0.16, 0.84), N=N)     # [S, C*Q, 3], [S, C*Q]
+            _mark("derived")
         chain, lnps = sampler.chain, sampler.lnprobability        # [S, W, niter, D], [S, W, niter]
         acc_frac = sampler.acceptance_fraction.mean(dim=1)
     else:
@@ -649,6 +676,8 @@ def fit_stars_gpu(catalog: StarCatalog, ic, indices, N=1, nwalkers=32, nburn=150
         rows[:, d0 + 3 * D] = dg.tau.amax(dim=1)
         rows[:, d0 + 3 * D + 1] = dg.rhat.amax(dim=1)
         rows[:, d0 + 3 * D + 2] = dg.window_ok.amin(dim=1)
+    if derived_props:
+        rows[:, -1 - 3 * len(derived_labels): -1] = dq.reshape(post.n_models, 3 * len(derived_labels))
     rows[:, -1] = good.to(torch.float64)
     rows[failed, :-1] = float("nan")
     out = rows.cpu().numpy()
@@ -967,7 +996,15 @@ def fit_catalog(catalog: StarCatalog, ic, N=1, fit_fn=None, checkpoint_dir=None,
     if not diagnostics:
         # an explicit False is the default: the same call, the same rows, the same checkpoint digest
         fit_kwargs = {k: v for k, v in fit_kwargs.items() if k != "diagnostics"}
-    columns = nested_result_columns(names) if nested else result_columns(names, diagnostics=diagnostics)
+    _, derived_labels = _derived_request(ic, fit_kwargs.get("derived"), N)
+    if derived_labels and nested:
+        raise ValueError("derived is for method='mcmc': a nested run stores no chain")
+    if derived_labels and fit_kwargs.get("fused", True) is False:
+        raise ValueError("derived needs the fused sampler (its stored chain is what the derived-properties kernel reads)")
+    if not derived_labels:
+        fit_kwargs = {k: v for k, v in fit_kwargs.items() if k != "derived"}
+    columns = (nested_result_columns(names) if nested else
+               result_columns(names, diagnostics=diagnostics, derived=derived_labels))
     width = len(columns)
     # (the digest of an MCMC shard is what it was before there was a method; a nested shard's carries the method)
     digest_kwargs = dict(fit_kwargs, method=method) if nested else fit_kwargs
@@ -1056,6 +1093,8 @@ def fit_catalog(catalog: StarCatalog, ic, N=1, fit_fn=None, checkpoint_dir=None,
         phases_extra = {"diag_s": phases.get("diagnostics", 0.0)}      # the diagnostics launch, apart from summary_s
     else:
         phases_extra = {}
+    if derived_labels:
+        phases_extra["derived_s"] = phases.get("derived", 0.0)         # the derived chain and its quantiles
     out.attrs["timings"] = {"fit_s": t_gather - t_fit, "gather_s": t_end - t_gather, "world": world, "rank": rank,
                             "backend": dist.get_backend() if distributed else None, "stars_of_this_rank": int(len(mine)),
                             # this rank's shard by phase: per-star blocks, start points, burn-in + sampling, summaries (+ D2H)

@@ -331,6 +331,54 @@ class FusedEnsembleSampler:
         """Split R-hat per parameter over the 2 W half-chains of each ensemble's walkers."""
         return self.diagnostics().rhat
 
+    def derived(self, ic, props, N=1):
+        """Model-grid columns ``props`` of ``ic`` at every stored sample: ``(derived, names)`` with ``derived`` a
+        [S, W, nsteps, C*Q] (model: [W, nsteps, C*Q]) CUDA view of the derived chain and ``names`` its columns
+        (:func:`isochrones_amd.derived.chain_derived`).  One ``iso_derived_chain`` launch per 8 columns on the
+        parameter-major storage, no copy; a model sampler and a catalog sampler alike."""
+        from . import derived as dv
+        if self._chain is None:
+            raise ValueError("no stored chain")
+        out, names = dv.chain_derived(self._chain, ic, props, N=N, n_ens=self.n_ensembles, nwalkers=self.nwalkers)
+        return (out if self._stacked else out[0]), names
+
+    def derived_quantiles(self, ic, props, q=(0.5, 0.16, 0.84), N=1, budget_bytes=None):
+        """Per-ensemble quantiles of the derived chain and its NaN counts: ``(quantiles, nan_count)``, [S, C*Q, len(q)]
+        float64 and [S, C*Q] int32 CUDA tensors (model: [C*Q, len(q)] and [C*Q]).  The derived chain is made in slices of
+        whole ensembles of at most ``budget_bytes`` (default ``derived.DERIVED_BUDGET_BYTES``), each slice by one
+        ``iso_derived_chain`` launch per 8 columns and summarised by one ``iso_chain_quantiles_layout`` call where it lies.
+        A column of an ensemble with a NaN sample (off the grid, or next to its NaN padding) has NaN quantiles."""
+        import ctypes as C
+        import torch
+        from . import _cabi, derived as dv, device as dev
+        if self._chain is None:
+            raise ValueError("no stored chain")
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        if q.size < 1 or q.size > 8:
+            raise ValueError("derived_quantiles takes 1 to 8 quantile levels per call (the quantile kernel's limit)")
+        budget = dv.DERIVED_BUDGET_BYTES if budget_bytes is None else int(budget_bytes)
+        labels, _ = dv.resolve_props(ic, props, N)
+        CQ = len(dv.components(ic, N)) * len(labels)
+        nsteps, S, W = int(self._chain.shape[0]), self.n_ensembles, self.nwalkers
+        per_ens = nsteps * CQ * W * 8
+        step = budget // per_ens
+        if step < 1:
+            raise ValueError("the derived chain of one ensemble takes %d bytes, more than budget_bytes = %d: raise the "
+                             "budget, ask for fewer columns or thin the chain" % (per_ens, budget))
+        chain = self._chain.contiguous()
+        out = torch.empty(S, CQ, q.size, dtype=torch.float64, device=self.device)
+        counts = torch.empty(S, CQ, dtype=torch.int32, device=self.device)
+        for s0 in range(0, S, step):
+            n = min(step, S - s0)
+            d, nc = dv.derive_storage(chain, S, W, ic, props, N=N, ens_begin=s0, n_ens_out=n)
+            _cabi.check(_cabi.lib().iso_chain_quantiles_layout(dev.context(self.device_index), dev.ptr(d),
+                                                               _cabi.CHAIN_PARAM_MAJOR, nsteps, n, W, CQ,
+                                                               q.ctypes.data_as(C.POINTER(C.c_double)), q.size,
+                                                               dev.ptr(out[s0:s0 + n]), dev.stream_ptr(self.device_index)))
+            counts[s0:s0 + n] = nc
+        out = torch.where((counts > 0)[:, :, None], torch.full_like(out, float("nan")), out)
+        return (out, counts) if self._stacked else (out[0], counts[0])
+
     def gelman_rubin(self):
         """Potential scale reduction factor R-hat per parameter across the independent ensembles of a multi-ensemble
         model sampler (Gelman & Rubin 1992: between- vs within-chain variance of the ensemble means; each ensemble's
