@@ -24,7 +24,7 @@
  * T < 4 or Wv == 0 gives NaN.
  *
  * Output.  out[(s * ndim + d) * 5 + i], i = ISO_DIAG_TAU, _WINDOW (M* as a double), _WINDOW_OK (1.0 or 0.0), _ESS,
- * _RHAT.  A NaN anywhere in the slab makes all five NaN.
+ * _RHAT.  A NaN or an infinity anywhere in the slab makes all five NaN (Inf - Inf in the centring makes A(0) NaN).
  *
  * Summation order of the device kernel (fixed, independent of the batch, so a pair's row is bit-identical alone or in
  * any batch): walker w belongs to group w mod 4; inside a group A(k) accumulates walker after walker in ascending w

@@ -1,6 +1,7 @@
 """iso_diag_chain_host (libiso_diag.so's plain C++ statement of the chain diagnostics) through ctypes against the numpy
 twin, on the shapes the GPU test uses; no GPU needed.  tau, ess and rhat within 1e-9 relative, window and window_ok
-exactly."""
+exactly.  Also the conditions the shared fixtures rest on: the tile size and LDS path each long shape was chosen for, and
+the open window of the c = 1000 evaluations."""
 import ctypes as C
 
 import numpy as np
@@ -31,6 +32,63 @@ def test_host_abi_matches_the_twin(lib, name):
     rc, got = _call(lib, np.ascontiguousarray(st), S, W, 5.0, max_lag)
     assert rc == 0, lib.iso_diag_last_error()
     tw.assert_matches(got, want)
+
+
+@pytest.mark.parametrize("name", tw.LONG_SHAPES)
+def test_every_lag_enters_tau(lib, name):
+    """tau sums rho(1..M*) only, so at c = 5 a lag sum beyond the window is invisible.  With c = 1000 the slowest
+    parameter's window stays open (open_window asserts window == K, window_ok == 0 on the twin) and all K lags count."""
+    st, (S, D, W, T, max_lag), want = tw.open_window(name)
+    rc, got = _call(lib, np.ascontiguousarray(st), S, W, tw.OPEN_C, max_lag)
+    assert rc == 0, lib.iso_diag_last_error()
+    tw.assert_matches(got, want)
+
+
+def test_long_shapes_get_the_tiles_they_were_chosen_for():
+    """The selection arithmetic of iso_diag_chain, replayed by tile_plan: an edit of a shape cannot silently stop reaching
+    its branch of the kernel."""
+    dims = {sh[0]: sh[1:] for sh in tw.SHAPES}
+    assert set(tw.PLANS) == set(tw.LONG_SHAPES)
+    for name, plan in tw.PLANS.items():
+        S, D, W, T, max_lag = dims[name]
+        assert tw.tile_plan(W, T, max_lag) == plan, name
+    lanes = {}                                                   # name -> lags per lane (1..4) of every quad of 256 lags
+    for name in tw.LONG_SHAPES:
+        K1 = min(dims[name][3] - 1, dims[name][4]) + 1
+        lanes[name] = [min(4, (K1 - 256 * q + 63) // 64) for q in range((K1 + 255) // 256)]
+    assert lanes == {"two_quads": [4, 3], "uneven_tiles": [4, 2], "large_lds": [4, 4, 4, 4, 1], "max_lag_mid_lane": [4, 2],
+                     "near_limit": [4, 4, 4, 4, 1]}
+    # tiles that start at a walker index that is no multiple of 4, and a partial last tile after more than two tiles
+    W, WT = dims["uneven_tiles"][2], tw.PLANS["uneven_tiles"][0]
+    assert [min(WT, W - w0) for w0 in range(0, W, WT)] == [5, 5, 5, 5, 1]
+    # max_lag binds inside a lane's lags: the lane's first lag is kept, a later one is summed and dropped
+    for name, dropped in (("max_lag_mid_lane", range(36, 64)), ("uneven_tiles", range(11, 64))):
+        K = dims[name][4]
+        assert [l for l in range(64) if 256 + l <= K < 256 + 64 + l] == list(dropped), name
+    # the library's two refusals, just past the shapes it takes
+    with pytest.raises(ValueError, match="exceed a CU's 160 KB"):
+        tw.tile_plan(1, 16400, 1024)
+    with pytest.raises(ValueError, match="nsteps too large"):
+        tw.tile_plan(2, 20481, 1024)
+    # every earlier shape stays inside 64 KB
+    assert not any(tw.tile_plan(W, T, ml)[2] for n, (S, D, W, T, ml) in dims.items() if n not in tw.PLANS)
+
+
+def test_a_nan_or_an_infinity_anywhere_makes_the_row_nan(lib):
+    st, (S, D, W, T, max_lag), want = tw.fixture("nonfinite")
+    assert np.isposinf(st[:, 0]).sum() == 1 and np.isneginf(st[:, 1]).sum() == 1 and not np.isnan(st).any()
+    assert np.isnan(want[0, :2]).all() and np.isfinite(want[0, 2]).all()
+    rc, got = _call(lib, np.ascontiguousarray(st), S, W, 5.0, max_lag)
+    assert rc == 0
+    tw.assert_matches(got, want)
+    clean = np.where(np.isfinite(st), st, 0.0)                           # the finite parameter does not see its neighbours
+    rc, alone = _call(lib, np.ascontiguousarray(clean), S, W, 5.0, max_lag)
+    assert rc == 0 and np.isfinite(alone).all()
+    assert np.array_equal(got[0, 2].view(np.int64), alone[0, 2].view(np.int64))
+    rows = np.ascontiguousarray(st.transpose(0, 2, 1))
+    rc, got_rows = _call(lib, rows, S, W, 5.0, max_lag, layout=_cabi.CHAIN_ROW_MAJOR, D=D)
+    assert rc == 0
+    tw.assert_matches(got_rows, want)
 
 
 def test_row_major_layout_and_python_surface(lib):

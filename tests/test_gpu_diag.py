@@ -1,7 +1,10 @@
 """iso_diag_chain (the HIP kernel of libiso_diag.so) on device tensors against the numpy twin: synthetic AR(1) chains
 written straight into parameter-major storage, tau / ess / rhat within 1e-9 relative, window and window_ok exactly;
-bit-identity of a star's row alone and in a batch; the diagnostics columns of a real catalog fit; the sampler methods
-after a single model's fit_mcmc."""
+bit-identity of a star's row alone and in a batch; the long shapes again with a window that never closes, so that every
+lag sum is seen; the row-major layout, the > 64 KB launch among small ones and the refusal past a CU's LDS through the C
+ABI; the diagnostics columns of a real catalog fit; the sampler methods after a single model's fit_mcmc."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -19,11 +22,106 @@ def _device(st, S, W, c=5.0, max_lag=1024):
     return out
 
 
+SENTINEL = -7.0
+
+
+def _abi(chain, layout, T, S, W, D, c=5.0, max_lag=1024):
+    """(rc, out [S, D, 5] on the device) of iso_diag_chain itself on a device tensor, on the current stream; out starts as
+    SENTINEL everywhere."""
+    import torch
+    from isochrones_amd import _diag_cabi, device as dev
+    out = torch.full((S, D, tw.NOUT), SENTINEL, dtype=torch.float64, device=chain.device)
+    rc = _diag_cabi.lib().iso_diag_chain(dev.ptr(chain), layout, T, S, W, D, c, max_lag, dev.ptr(out),
+                                         dev.stream_ptr(chain.device.index))
+    torch.cuda.synchronize()
+    return rc, out
+
+
 @pytest.mark.parametrize("name", [sh[0] for sh in tw.SHAPES])
 def test_kernel_matches_the_twin(name):
     st, (S, D, W, T, max_lag), want = tw.fixture(name)
     got = _device(st, S, W, 5.0, max_lag).cpu().numpy()
     tw.assert_matches(got, want)
+
+
+@pytest.mark.parametrize("name", tw.LONG_SHAPES)
+def test_every_lag_enters_tau(name):
+    """tau sums rho(1..M*) only, so at c = 5 a wrong lag sum beyond the window changes nothing.  With c = 1000 the slowest
+    parameter's window stays open (open_window asserts window == K, window_ok == 0 on the twin) and all K lags count."""
+    st, (S, D, W, T, max_lag), want = tw.open_window(name)
+    got = _device(st, S, W, tw.OPEN_C, max_lag).cpu().numpy()
+    tw.assert_matches(got, want)
+
+
+@pytest.mark.parametrize("name", ["plain", "reference", "uneven_tiles"])
+def test_row_major_chain_on_the_device(name):
+    """ISO_DIAG_ROW_MAJOR ([T][S * W][D]) reaches the kernel through the C ABI only.  The layout changes the addresses a
+    tile is staged from, not the order of any sum: the result is the parameter-major one bit for bit."""
+    import torch
+    from isochrones_amd import _cabi
+    st, (S, D, W, T, max_lag), want = tw.fixture(name)
+    cols = torch.as_tensor(np.array(st), device="cuda")
+    rows = cols.permute(0, 2, 1).contiguous()
+    rc, by_param = _abi(cols, _cabi.CHAIN_PARAM_MAJOR, T, S, W, D, 5.0, max_lag)
+    assert rc == 0
+    rc, by_row = _abi(rows, _cabi.CHAIN_ROW_MAJOR, T, S, W, D, 5.0, max_lag)
+    assert rc == 0
+    assert torch.equal(by_row.view(torch.int64), by_param.view(torch.int64))
+    tw.assert_matches(by_row.cpu().numpy(), want)
+
+
+def test_large_lds_launch_between_small_ones():
+    """The > 64 KB launch raises a function attribute of the kernel; a small launch after it, and the large one again,
+    give what they give on their own."""
+    import torch
+    big, (S, D, W, T, max_lag), want_big = tw.fixture("large_lds")
+    small, (s, d, w, t, ml), want_small = tw.fixture("plain")
+    assert tw.tile_plan(W, T, max_lag)[2] and not tw.tile_plan(w, t, ml)[2]
+    first = _device(big, S, W, 5.0, max_lag)
+    between = _device(small, s, w, 5.0, ml)
+    third = _device(big, S, W, 5.0, max_lag)
+    assert torch.equal(first.view(torch.int64), third.view(torch.int64))
+    tw.assert_matches(first.cpu().numpy(), want_big)
+    tw.assert_matches(between.cpu().numpy(), want_small)
+
+
+def test_shape_just_past_a_cus_lds_is_refused():
+    """One walker of 16 400 steps needs 164 056 bytes of LDS, 216 more than a CU has: refused on the host with a text,
+    before any launch, out untouched.  (near_limit, 160 856 bytes, is answered.)"""
+    import torch
+    from isochrones_amd import _cabi, _diag_cabi
+    with pytest.raises(ValueError, match="exceed a CU's 160 KB"):
+        tw.tile_plan(1, 16400, 1024)
+    chain = torch.zeros(16400, 1, 1, dtype=torch.float64, device="cuda")
+    rc, out = _abi(chain, _cabi.CHAIN_PARAM_MAJOR, 16400, 1, 1, 1)
+    assert rc == -1                                                      # ISO_DIAG_ERR_INVALID
+    assert "exceed a CU's 160 KB" in _diag_cabi.lib().iso_diag_last_error().decode()
+    assert (out == SENTINEL).all()
+    with pytest.raises(ia.IsoError, match="exceed a CU's 160 KB"):
+        ia.chain_diagnostics(chain, n_ens=1, nwalkers=1)
+    torch.cuda.synchronize()                                             # nothing was launched that could fail
+
+
+def test_two_steps():
+    """T = 2: K = 1 and the window closes at M = 1 = T - 1, where tau is zero in exact arithmetic (rho(1) = -1/2): ess is
+    W T over rounding noise and is not compared.  No split chain has two steps, so rhat is NaN."""
+    st = np.random.default_rng(23).standard_normal((2, 2, 5))
+    got = _device(st, 1, 5).cpu().numpy()
+    assert got.shape == (1, 2, tw.NOUT)
+    assert (got[..., tw.WINDOW] == 1).all() and (got[..., tw.WINDOW_OK] == 1).all()
+    assert np.isnan(got[..., tw.RHAT]).all()
+    assert (np.abs(got[..., tw.TAU]) <= 1e-12).all(), got[..., tw.TAU]
+
+
+def test_a_nan_or_an_infinity_anywhere_makes_the_row_nan():
+    import torch
+    st, (S, D, W, T, max_lag), want = tw.fixture("nonfinite")
+    assert np.isnan(want[0, :2]).all() and np.isfinite(want[0, 2]).all()
+    got = _device(st, S, W, 5.0, max_lag)
+    tw.assert_matches(got.cpu().numpy(), want)
+    clean = _device(np.where(np.isfinite(st), st, 0.0), S, W, 5.0, max_lag)   # the finite parameter does not see the others
+    assert torch.isfinite(clean).all()
+    assert torch.equal(got[0, 2].view(torch.int64), clean[0, 2].view(torch.int64))
 
 
 def test_other_window_factor_and_max_lag():
@@ -35,7 +133,7 @@ def test_other_window_factor_and_max_lag():
     tw.assert_matches(_device(sub, 1, W, 3.0, 7).cpu().numpy(), want)
 
 
-@pytest.mark.parametrize("name", ["reference", "edge_pairs", "plain"])
+@pytest.mark.parametrize("name", ["reference", "edge_pairs", "plain", "large_lds", "uneven_tiles"])
 def test_a_row_is_bit_identical_alone_and_in_a_batch(name):
     import torch
     st, (S, D, W, T, max_lag), _ = tw.fixture(name)
