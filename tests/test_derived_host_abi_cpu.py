@@ -1,6 +1,6 @@
 """iso_derived_chain_host (libiso_derived.so's plain C++ statement of the derived chain) through ctypes against the numpy
 twin, on the shapes the GPU test uses; no GPU needed.  Values within 1e-12 (1 + |b|), NaN positions and nan_count
-exactly."""
+exactly; and bit for bit for every Q and every component-reuse pattern."""
 import ctypes as C
 
 import numpy as np
@@ -51,6 +51,7 @@ def test_host_abi_matches_the_twin(lib, S, W, T, Q, Cn):
     rc, full, nan_count = call_host(lib, x, tw.PARAM_MAJOR, S, W, cols, axes, comps)
     assert rc == 0, lib.iso_derived_last_error()
     assert tw.close(full, want)
+    assert tw.same_bits(full, want)
     np.testing.assert_array_equal(nan_count, want_nan)
     rows = np.ascontiguousarray(x.transpose(0, 2, 1))
     rc, got_r, nan_r = call_host(lib, rows, tw.ROW_MAJOR, S, W, cols, axes, comps)
@@ -68,6 +69,24 @@ def test_host_abi_matches_the_twin(lib, S, W, T, Q, Cn):
         np.testing.assert_array_equal(nan_sub, tw_nan)
 
 
+@pytest.mark.parametrize("S,W,T", [tw.EDGE_SHAPES[0], tw.EDGE_SHAPES[3]])
+@pytest.mark.parametrize("Q", range(1, 9))
+def test_host_abi_is_the_twin_bit_for_bit(lib, S, W, T, Q):
+    """Every Q, every reuse pattern, both table kinds, on a two-chunk shape and on the 2 100-step one: the plain C++
+    statement and the numpy one are the same float64 operations, so they agree in every bit, not within 1e-12."""
+    for kind in ("track", "iso"):
+        cols, axes = tw.packed(kind, Q)
+        x = np.array(tw.chain7(kind, S, W, T))
+        for comps in tw.COMP_PATTERNS:
+            want, want_nan = tw.derive(x, tw.PARAM_MAJOR, S, W, cols, axes, comps)
+            rc, got, nan_count = call_host(lib, x, tw.PARAM_MAJOR, S, W, cols, axes, comps)
+            assert rc == 0, lib.iso_derived_last_error()
+            assert tw.close(got, want), (kind, comps)
+            assert tw.same_bits(got, want), (kind, comps)
+            np.testing.assert_array_equal(nan_count, want_nan)
+            assert np.isfinite(want).mean() > 0.5 and np.isnan(want).mean() > 0.05
+
+
 def test_rules_through_the_host_abi(lib):
     cols, axes = tw.rule_table()
     pts = np.array([(0.5, 15.0, 3.0), (1.0, 20.0, 2.0), (2.0, 15.0, 3.0), (0.5, 40.0, 3.0), (0.5, 15.0, 8.0), (-0.1, 15.0, 3.0),
@@ -79,6 +98,12 @@ def test_rules_through_the_host_abi(lib):
     np.testing.assert_array_equal(out[0].T, want)
     np.testing.assert_array_equal(out[0, :, :5].T, [[56.5, 2.5], [111.0, 2.5], [206.5, 3.25], [71.5, 3.25], [58.0, 5.75]])
     np.testing.assert_array_equal(nan_count, [[5, 5]])
+    # every query of the twin's rule test, with its exact numbers
+    pts = np.array([q for q, _ in tw.RULES])
+    x = np.ascontiguousarray(pts.T[None])
+    rc, out, nan_count = call_host(lib, x, tw.PARAM_MAJOR, 1, len(pts), cols, axes, [(0, 1, 2)])
+    assert rc == 0
+    np.testing.assert_array_equal(out[0].T, [w for _, w in tw.RULES])
 
 
 def test_bad_arguments_are_refused(lib):

@@ -52,33 +52,44 @@ def test_derive_is_the_interpolator_per_component_and_counts_nans():
     np.testing.assert_array_equal(nan_sub, nan_count[1:])
 
 
-def _at(x0, x1, xk):
-    cols, axes = tw.rule_table()
-    return tw.interp(cols, axes, np.array([x0]), np.array([x1]), np.array([xk]))[0]
-
-
 def test_rules_on_a_hand_built_table():
-    nan = np.nan
-    # inside, the last axis non-uniform: xk = 3 lies halfway between the nodes 2 and 4
-    np.testing.assert_array_equal(_at(0.5, 15.0, 3.0), [56.5, 2.5])
-    np.testing.assert_array_equal(_at(0.25, 35.0, 7.0), [25.0 + 17.5 + 2.75, 1.0 + 0.25 * 1.75 + 0.5 * (0.25 * 4 + 0.75 * 9)])
-    # on a node: the cell above it, weight 0 on every other corner
-    np.testing.assert_array_equal(_at(1.0, 20.0, 2.0), [111.0, 2.5])
-    np.testing.assert_array_equal(_at(0.0, 10.0, 1.0), [0.0, 1.0])
-    # on the last node of each axis: the cell below, weight 1
-    np.testing.assert_array_equal(_at(2.0, 15.0, 3.0), [206.5, 1.0 + 1.0 + 1.25])
-    np.testing.assert_array_equal(_at(0.5, 40.0, 3.0), [71.5, 1.0 + 1.0 + 1.25])
-    np.testing.assert_array_equal(_at(0.5, 15.0, 8.0), [58.0, 1.25 + 4.5])
-    # off either end of each axis, and a NaN coordinate
-    for q in ((-0.1, 15.0, 3.0), (2.1, 15.0, 3.0), (0.5, 9.0, 3.0), (0.5, 41.0, 3.0), (0.5, 15.0, 0.5), (0.5, 15.0, 8.5),
-              (nan, 15.0, 3.0), (0.5, nan, 3.0), (0.5, 15.0, nan)):
-        np.testing.assert_array_equal(_at(*q), [nan, nan])
-    # the NaN node (2, 2, 3): a corner of the cell above (1, 1, 2) with weight zero, and the last node itself
-    np.testing.assert_array_equal(_at(1.0, 20.0, 4.0), [nan, nan])
-    np.testing.assert_array_equal(_at(2.0, 40.0, 8.0), [nan, nan])
-    np.testing.assert_array_equal(_at(1.5, 30.0, 6.0), [nan, nan])           # inside the cell that has it
-    np.testing.assert_array_equal(_at(1.0, 20.0, 3.0), [111.5, 3.25])         # the cell below it along the last axis
-    np.testing.assert_array_equal(_at(0.5, 15.0, 6.0), [50.0 + 5.0 + 2.5, 1.25 + 0.5 * 6.5])     # a cell away from it
+    cols, axes = tw.rule_table()
+    for (x0, x1, xk), want in tw.RULES:
+        got = tw.interp(cols, axes, np.array([x0]), np.array([x1]), np.array([xk]))[0]
+        np.testing.assert_array_equal(got, want, err_msg=repr((x0, x1, xk)))
+    assert sum(np.isnan(w[0]) for _, w in tw.RULES) == 12 and len(tw.RULES) == 21
+
+
+@pytest.mark.parametrize("kind", ["track", "iso"])
+def test_twin_stays_within_the_rounding_bound_of_long_double(kind, capsys):
+    """The 1e-12 of this file passes a contracted product or another summation order; tw.LD_BOUND (derived in
+    tw.interp_ld) does not leave that room.  Q = 8 on the two-chunk shape, every reuse pattern's components."""
+    S, W, T = tw.EDGE_SHAPES[0]
+    cols, axes = tw.packed(kind, 8)
+    x = tw.chain7(kind, S, W, T)
+    worst = 0.0
+    for comps in tw.COMP_PATTERNS[:3]:
+        got, _ = tw.derive(x, tw.PARAM_MAJOR, S, W, cols, axes, comps)
+        ref, cmax = tw.derive_ld(x, tw.PARAM_MAJOR, S, W, cols, axes, comps)
+        np.testing.assert_array_equal(np.isnan(got), np.isnan(ref))
+        assert np.isfinite(got).mean() > 0.5 and np.isnan(got).mean() > 0.05
+        worst = max(worst, tw.ld_ratio(got, ref, cmax))
+    with capsys.disabled():
+        print("\ntwin against long double, %s, Q = 8: worst %.2f units of 2^-52 cmax (bound %d)" % (kind, worst, tw.LD_BOUND))
+    assert worst <= tw.LD_BOUND
+
+
+def test_search_fixtures_hold_what_they_say():
+    for axis, n in [(2, n) for n in (2, 3, 5, 16, 17, 65)] + [(0, 2), (0, 7), (1, 2), (1, 3)]:
+        cols, axes = tw.search_table(axis, n)
+        x, want = tw.search_samples(axis, n)
+        got = tw.interp(cols, axes, *x)[:, 0]
+        node = want >= 0
+        assert node.sum() == n and want[n - 1] == n - 1
+        np.testing.assert_array_equal(got[node], want[node])
+        assert np.isnan(got[np.isnan(want)]).all() and np.isnan(want).sum() == 2
+        np.testing.assert_array_equal(got[want == -1][:n - 1], np.arange(n - 1) + 0.5)       # t = 0.5 at a midpoint
+        assert np.isfinite(got[want == -1]).all()
 
 
 def test_bracket_rules():

@@ -2,52 +2,14 @@
 star's derived values across batch, ensemble range and layout, the call forms of ia.chain_derived, the derived columns of
 a real catalog fit against numpy.percentile of the derived chain, budget slicing, NaN reporting, a binary (N = 2) and the
 sampler methods after a single model's fit_mcmc."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import isochrones_amd as ia
-from isochrones_amd import _cabi, _derived_cabi
 from tests import _derived_twin as tw
+from tests._derived_gpu import device as _device, host as _host
 
 pytestmark = pytest.mark.gpu
-
-
-def _device(x, layout, S, W, cols, axes, comps, ens_begin=0, n_out=None):
-    """The kernel on host arrays copied to the device -> (out, nan_count) as numpy arrays."""
-    import torch
-    from isochrones_amd import device as dev
-    n_out = S - ens_begin if n_out is None else n_out
-    T = x.shape[0]
-    ndim = x.shape[1] if layout == tw.PARAM_MAJOR else x.shape[2]
-    d_cols, d_x = torch.as_tensor(cols, device="cuda"), torch.as_tensor(np.array(x), device="cuda")
-    d_ax = [torch.as_tensor(a, device="cuda") for a in axes]
-    table = _derived_cabi.IsoDerivedTable(d_cols.data_ptr(), d_ax[0].data_ptr(), d_ax[1].data_ptr(), d_ax[2].data_ptr(),
-                                          *cols.shape)
-    Cn, Q = len(comps), cols.shape[3]
-    carr = (C.c_int32 * (3 * Cn))(*[i for comp in comps for i in comp])
-    out = torch.full((T, Cn * Q, n_out * W), -7.0, dtype=torch.float64, device="cuda")
-    nan_count = torch.full((n_out, Cn * Q), -7, dtype=torch.int32, device="cuda")
-    _derived_cabi.check(_derived_cabi.lib().iso_derived_chain(C.byref(table), dev.ptr(d_x), layout, T, S, W, ndim, ens_begin,
-                                                              n_out, carr, Cn, dev.ptr(out), dev.ptr(nan_count),
-                                                              dev.stream_ptr(0)))
-    torch.cuda.synchronize()
-    return out.cpu().numpy(), nan_count.cpu().numpy()
-
-
-def _host(x, layout, S, W, cols, axes, comps):
-    table = _derived_cabi.IsoDerivedTable(cols.ctypes.data, axes[0].ctypes.data, axes[1].ctypes.data, axes[2].ctypes.data,
-                                          *cols.shape)
-    Cn, Q = len(comps), cols.shape[3]
-    carr = (C.c_int32 * (3 * Cn))(*[i for comp in comps for i in comp])
-    out = np.empty((x.shape[0], Cn * Q, S * W))
-    nan_count = np.empty((S, Cn * Q), dtype=np.int32)
-    rc = _derived_cabi.lib().iso_derived_chain_host(C.byref(table), x.ctypes.data_as(C.c_void_p), layout, x.shape[0], S, W, 6,
-                                                    0, S, carr, Cn, out.ctypes.data_as(C.c_void_p),
-                                                    nan_count.ctypes.data_as(C.c_void_p), None)
-    assert rc == 0
-    return out, nan_count
 
 
 def _bits(a):
