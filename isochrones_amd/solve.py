@@ -23,14 +23,15 @@ def column_ranges(col, name="column"):
     if col.ndim != 3:
         raise ValueError("column_ranges needs a [n0, n1, nk] array")
     nk = col.shape[2]
+    fin = np.isfinite(col)
     with np.errstate(invalid="ignore"):
-        down = np.diff(col, axis=2) < 0                     # NaN (padding, holes) compares False
+        # between finite neighbours only: padding and holes (NaN or inf) are no steps, columns with one walk the range
+        down = (np.diff(col, axis=2) < 0) & fin[:, :, 1:] & fin[:, :, :-1]
     if down.any():
         i, j, k = (int(v) for v in np.argwhere(down)[0])
         raise ValueError("solve_eep needs '%s' nondecreasing along the last axis of the table, but at (i, j, k) = "
                          "(%d, %d, %d) it falls from %r to %r; use the Nelder-Mead path for this table "
                          "(get_eep(..., accurate=True) / get_eep_accurate)" % (name, i, j, k + 1, col[i, j, k], col[i, j, k + 1]))
-    fin = np.isfinite(col)
     some = fin.any(axis=2)
     first = np.where(some, fin.argmax(axis=2), nk)
     last = np.where(some, nk - 1 - fin[:, :, ::-1].argmax(axis=2), -1)

@@ -29,13 +29,36 @@ def _cell(ax, x):
     return np.clip(np.searchsorted(ax, x, side="right") - 1, 0, ax.size - 2)
 
 
+def knot_values(grid, axes, icol, x0, x1, nthreads=1):
+    """g[n, nk]: the oracle interpolator's value of column ``icol`` at (x0, x1, axk[k]) for every knot k."""
+    table = orc.OracleTable(grid, axes)
+    axk = table.axes[2]
+    x0, x1 = np.asarray(x0, dtype=float).ravel(), np.asarray(x1, dtype=float).ravel()
+    m, nk = x0.size, axk.size
+    return table.interp([np.repeat(x0, nk), np.repeat(x1, nk), np.tile(axk, m)], [icol], nthreads=nthreads).reshape(m, nk)
+
+
+def cell_ranges(col, axes, x0, x1):
+    """(ok, i, j, F, L) per query: inside both axes, the cell the interpolator uses (cell 0 where not ok) and the
+    intersection [F, L] of its four corner columns' finite ranges (F > L: empty)."""
+    ax0, ax1 = np.asarray(axes[0], dtype=float), np.asarray(axes[1], dtype=float)
+    first, last = finite_ranges(np.asarray(col, dtype=float))
+    a, b = np.asarray(x0, dtype=float).ravel(), np.asarray(x1, dtype=float).ravel()
+    with np.errstate(invalid="ignore"):
+        ok = np.isfinite(a) & np.isfinite(b) & (a >= ax0[0]) & (a <= ax0[-1]) & (b >= ax1[0]) & (b <= ax1[-1])
+    i = _cell(ax0, np.where(ok, a, ax0[0]))
+    j = _cell(ax1, np.where(ok, b, ax1[0]))
+    F = np.maximum.reduce([first[i, j], first[i, j + 1], first[i + 1, j], first[i + 1, j + 1]])
+    L = np.minimum.reduce([last[i, j], last[i, j + 1], last[i + 1, j], last[i + 1, j + 1]])
+    return ok, i, j, F, L
+
+
 def solve(grid, axes, icol, x0, x1, target, chunk=256, nthreads=1):
     """grid[n0, n1, nk, ncol], axes (ax0, ax1, axk), column number -> (e, g_lo, g_hi, k_star) per query: the solution,
     the two knot values it was inverted between (NaN where no segment was inverted) and k* (-1: none)."""
-    table = orc.OracleTable(grid, axes)
-    ax0, ax1, axk = table.axes
+    grid = np.asarray(grid, dtype=float)
+    axk = np.ascontiguousarray(axes[2], dtype=float)
     nk = axk.size
-    first, last = finite_ranges(table.grid[..., icol])
     x0, x1, target = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=float), np.broadcast(x0, x1, target).shape)
                                            .ravel()) for v in (x0, x1, target)]
     n = x0.size
@@ -45,13 +68,8 @@ def solve(grid, axes, icol, x0, x1, target, chunk=256, nthreads=1):
     ks = np.arange(nk)
     for s in range(0, n, chunk):
         a, b, y = x0[s:s + chunk], x1[s:s + chunk], target[s:s + chunk]
-        m = a.size
-        g = table.interp([np.repeat(a, nk), np.repeat(b, nk), np.tile(axk, m)], [icol], nthreads=nthreads).reshape(m, nk)
-        ok = np.isfinite(a) & np.isfinite(b) & (a >= ax0[0]) & (a <= ax0[-1]) & (b >= ax1[0]) & (b <= ax1[-1])
-        i = _cell(ax0, np.where(ok, a, ax0[0]))
-        j = _cell(ax1, np.where(ok, b, ax1[0]))
-        F = np.maximum.reduce([first[i, j], first[i, j + 1], first[i + 1, j], first[i + 1, j + 1]])
-        L = np.minimum.reduce([last[i, j], last[i, j + 1], last[i + 1, j], last[i + 1, j + 1]])
+        g = knot_values(grid, axes, icol, a, b, nthreads=nthreads)
+        ok, _, _, F, L = cell_ranges(grid[..., icol], axes, a, b)
         with np.errstate(invalid="ignore"):
             reach = (g >= y[:, None]) & (ks[None, :] >= F[:, None]) & (ks[None, :] <= L[:, None]) & ok[:, None]
         for r in np.flatnonzero(reach.any(axis=1)):
@@ -65,7 +83,8 @@ def solve(grid, axes, icol, x0, x1, target, chunk=256, nthreads=1):
             if np.isnan(lo):
                 continue
             g_lo[s + r], g_hi[s + r] = lo, hi
-            e[s + r] = axk[k - 1] + (y[r] - lo) / (hi - lo) * (axk[k] - axk[k - 1])
+            with np.errstate(invalid="ignore"):
+                e[s + r] = axk[k - 1] + (y[r] - lo) / (hi - lo) * (axk[k] - axk[k - 1])
     return e, g_lo, g_hi, k_star
 
 

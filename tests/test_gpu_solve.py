@@ -13,6 +13,7 @@ from isochrones_amd.models import (EvolutionTrackGrid, EvolutionTrackInterpolato
                                    _bc)
 from tests import _solve_cases as K
 from tests import _solve_twin as T
+from tests._solve_gpu import same
 
 pytestmark = pytest.mark.gpu
 
@@ -97,6 +98,8 @@ def test_device_against_the_twin_on_mist_shaped_tables(kind):
         kind, trip.max(), diff.max(), np.abs(e_dev[fin] - e_twin[fin]).max()))
     assert trip.max() <= 1e-10
     assert diff.max() <= 1e-10
+    # the kernel performs the twin's float64 operations in the twin's order, without contraction: every bit agrees
+    assert same(e_dev, e_twin, (dfi.grid[..., icol], axes, x0, x1, y))
 
 
 def orc_threads():
