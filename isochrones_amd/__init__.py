@@ -19,5 +19,6 @@ from .starfit import starfit, batch_starfit
 from .cluster import StarClusterModel, simulate_cluster
 from .diagnostics import chain_diagnostics, ChainDiagnostics
 from .derived import chain_derived
+from .predictive import chain_predictive
 
 __version__ = "0.1.0"

@@ -133,7 +133,7 @@ class CatalogPosterior:
             # template descriptor + plain per-star columns; the device fills the per-star constant blocks
             self.models = None
             template = _template
-            col = _columns
+            col = self._columns = _columns
             n = int(col["mag_val"].shape[0])
             D = template.n_params
             d0 = template.model_desc()
@@ -511,12 +511,14 @@ DIAG_STATS = ("tau", "ess", "rhat")
 DIAG_TAIL = ("tau_max", "rhat_max", "window_ok")
 
 
-def result_columns(param_names, diagnostics=False, derived=()):
+def result_columns(param_names, diagnostics=False, derived=(), predictive=()):
     """Columns of an MCMC result row.  ``diagnostics=True`` adds, between ``acceptance`` and ``ok`` (which stays last), the
     per-parameter ``{p}_tau, {p}_ess, {p}_rhat`` and the per-star ``tau_max``, ``rhat_max`` and ``window_ok`` (the minimum
     over the parameters: 1 only where every parameter's autocorrelation window was found).  ``derived``: the labels of
     derived properties, already expanded (``{label}_{k}`` for N > 1, :func:`isochrones_amd.derived.expand_labels`); each adds
-    ``{label}_median, _p16, _p84`` after the diagnostics columns and before ``ok``."""
+    ``{label}_median, _p16, _p84`` after the diagnostics columns and before ``ok``.  ``predictive``: the bands of a
+    posterior-predictive check; adds, after the derived columns and before ``ok``, ``ppc``, ``ppc_nbad``, per band
+    ``{band}_mag_median, _p16, _p84``, ``chi2_{term}`` for every band and Teff, logg, feh, parallax, and ``map_{param}``."""
     cols = []
     for p in param_names:
         cols += ["%s_%s" % (p, s) for s in RESULT_STATS]
@@ -527,7 +529,16 @@ def result_columns(param_names, diagnostics=False, derived=()):
         cols += list(DIAG_TAIL)
     for label in derived:
         cols += ["%s_%s" % (label, s) for s in RESULT_STATS]
+    if predictive:
+        from .predictive import result_labels
+        cols += result_labels(tuple(predictive), param_names)
     return cols + ["ok"]
+
+
+def _predictive_bands(catalog, ic):
+    """The bands a posterior-predictive check of this catalog's fits compares: the catalog's that the BC grid has, in the
+    catalog's order (the order of a fit's magnitude columns)."""
+    return tuple(b for b in catalog.bands if b in ic.bc_grid.bands)
 
 
 def _derived_request(ic, derived, N):
@@ -544,7 +555,7 @@ def _derived_request(ic, derived, N):
 
 def fit_stars_gpu(catalog: StarCatalog, ic, indices, N=1, nwalkers=32, nburn=150, niter=100, seed=0,
                   model_kwargs=None, fused=True, timings=None, max_stars_per_batch=200_000, return_chains=False,
-                  replay_record=None, diagnostics=False, derived=None):
+                  replay_record=None, diagnostics=False, derived=None, predictive=False):
     """Fit the stars ``indices`` of the catalog on the current GPU; returns [len(indices), 3*D+3]
     float64 numpy rows (result_columns order).  ``diagnostics=True`` (fused sampler): 3*D+3 more columns, the stored
     chain's per-parameter autocorrelation time, effective sample size and split R-hat and their per-star summary
@@ -552,7 +563,9 @@ def fit_stars_gpu(catalog: StarCatalog, ic, indices, N=1, nwalkers=32, nburn=150
     ``derived`` (fused sampler): a sequence of model-grid column names or ``(label, column)`` pairs, or ``True`` for those of
     mass, radius, age, Teff, logg the grid has and the fit does not sample; per label three more columns, the median, 16th
     and 84th percentile of that property over the star's chain (the libiso_derived.so kernel on the chain where it lies,
-    then the quantile kernel), NaN where a sample of the star fell off the grid.  ``return_chains=True`` (fused sampler, one batch): also the
+    then the quantile kernel), NaN where a sample of the star fell off the grid.  ``predictive=True`` (fused sampler): the
+    posterior-predictive check of every star against its own measurements (the libiso_predict.so kernel on the chain where it
+    lies; the columns of ``result_columns(..., predictive=bands)``).  ``return_chains=True`` (fused sampler, one batch): also the
     stored chain [S, W, niter, D] and its lnpost values [S, W, niter] as CUDA tensors.  ``replay_record`` (a dict, tests):
     filled with what a move-by-move replay of the SAMPLING run needs - the ensembles as burn-in left them (``pos`` [S, W, D],
     ``lnp`` [S, W]), the sampler's ``seed``, the step counter the run starts at (``step0`` = nburn), the start points."""
@@ -573,6 +586,11 @@ def fit_stars_gpu(catalog: StarCatalog, ic, indices, N=1, nwalkers=32, nburn=150
         raise ValueError("derived needs the fused sampler (its stored chain is what the derived-properties kernel reads)")
     n_diag = 3 * (N + 4) + 3 if diagnostics else 0          # columns between acceptance and ok
     n_diag += 3 * len(derived_labels)
+    if predictive and not fused:
+        raise ValueError("predictive needs the fused sampler (its stored chain is what the posterior-predictive kernel reads)")
+    pbands = _predictive_bands(catalog, ic) if predictive else ()
+    n_pred = (2 + 3 * len(pbands) + len(pbands) + 4 + (N + 4)) if predictive else 0
+    n_diag += n_pred
     if len(indices) == 0:
         return np.empty((0, 3 * (N + 4) + 3 + n_diag))
     if return_chains and (not fused or len(indices) > max_stars_per_batch):
@@ -582,7 +600,7 @@ def fit_stars_gpu(catalog: StarCatalog, ic, indices, N=1, nwalkers=32, nburn=150
         parts = [fit_stars_gpu(catalog, ic, indices[k:k + max_stars_per_batch], N=N, nwalkers=nwalkers, nburn=nburn,
                                niter=niter, seed=seed + 7919 * (k // max_stars_per_batch), model_kwargs=model_kwargs,
                                fused=fused, timings=timings, max_stars_per_batch=max_stars_per_batch,
-                               diagnostics=diagnostics, derived=derived)
+                               diagnostics=diagnostics, derived=derived, predictive=predictive)
                  for k in range(0, len(indices), max_stars_per_batch)]
         return np.concatenate(parts, axis=0)
     post = CatalogPosterior.from_catalog(catalog, ic, N=N, indices=indices, **(model_kwargs or {}))
@@ -635,6 +653,11 @@ def fit_stars_gpu(catalog: StarCatalog, ic, indices, N=1, nwalkers=32, nburn=150
         if derived_props:
             dq, dnan = sampler.derived_quantiles(ic, derived_props, (0.5, 0.16, 0.84), N=N)     # [S, C*Q, 3], [S, C*Q]
             _mark("derived")
+        if predictive:
+            if tuple(post.template.bands) != pbands:
+                raise ValueError("the fit's bands %s are not the catalog's %s" % (tuple(post.template.bands), pbands))
+            pp = sampler.predictive(ic, post._columns, bands=pbands, q=(0.5, 0.16, 0.84), N=N)
+            _mark("predictive")
         chain, lnps = sampler.chain, sampler.lnprobability        # [S, W, niter, D], [S, W, niter]
         acc_frac = sampler.acceptance_fraction.mean(dim=1)
     else:
@@ -677,7 +700,16 @@ def fit_stars_gpu(catalog: StarCatalog, ic, indices, N=1, nwalkers=32, nburn=150
         rows[:, d0 + 3 * D + 1] = dg.rhat.amax(dim=1)
         rows[:, d0 + 3 * D + 2] = dg.window_ok.amin(dim=1)
     if derived_props:
-        rows[:, -1 - 3 * len(derived_labels): -1] = dq.reshape(post.n_models, 3 * len(derived_labels))
+        d1 = rows.shape[1] - 1 - n_pred
+        rows[:, d1 - 3 * len(derived_labels): d1] = dq.reshape(post.n_models, 3 * len(derived_labels))
+    if predictive:
+        p0 = rows.shape[1] - 1 - n_pred
+        nb = len(pbands)
+        rows[:, p0] = pp["ppc"]
+        rows[:, p0 + 1] = pp["n_bad"].to(torch.float64)
+        rows[:, p0 + 2: p0 + 2 + 3 * nb] = pp["mag_quantiles"].reshape(post.n_models, 3 * nb)
+        rows[:, p0 + 2 + 3 * nb: p0 + 2 + 4 * nb + 4] = pp["term_chi2"]
+        rows[:, p0 + 2 + 4 * nb + 4: -1] = pp["map_pars"]
     rows[:, -1] = good.to(torch.float64)
     rows[failed, :-1] = float("nan")
     out = rows.cpu().numpy()
@@ -1003,8 +1035,16 @@ def fit_catalog(catalog: StarCatalog, ic, N=1, fit_fn=None, checkpoint_dir=None,
         raise ValueError("derived needs the fused sampler (its stored chain is what the derived-properties kernel reads)")
     if not derived_labels:
         fit_kwargs = {k: v for k, v in fit_kwargs.items() if k != "derived"}
+    predictive = bool(fit_kwargs.get("predictive", False))
+    if predictive and nested:
+        raise ValueError("predictive is for method='mcmc': a nested run stores no chain")
+    if predictive and fit_kwargs.get("fused", True) is False:
+        raise ValueError("predictive needs the fused sampler (its stored chain is what the posterior-predictive kernel reads)")
+    if not predictive:
+        fit_kwargs = {k: v for k, v in fit_kwargs.items() if k != "predictive"}
     columns = (nested_result_columns(names) if nested else
-               result_columns(names, diagnostics=diagnostics, derived=derived_labels))
+               result_columns(names, diagnostics=diagnostics, derived=derived_labels,
+                              predictive=_predictive_bands(catalog, ic) if predictive else ()))
     width = len(columns)
     # (the digest of an MCMC shard is what it was before there was a method; a nested shard's carries the method)
     digest_kwargs = dict(fit_kwargs, method=method) if nested else fit_kwargs
@@ -1095,6 +1135,8 @@ def fit_catalog(catalog: StarCatalog, ic, N=1, fit_fn=None, checkpoint_dir=None,
         phases_extra = {}
     if derived_labels:
         phases_extra["derived_s"] = phases.get("derived", 0.0)         # the derived chain and its quantiles
+    if predictive:
+        phases_extra["predictive_s"] = phases.get("predictive", 0.0)   # the posterior-predictive launch and its quantiles
     out.attrs["timings"] = {"fit_s": t_gather - t_fit, "gather_s": t_end - t_gather, "world": world, "rank": rank,
                             "backend": dist.get_backend() if distributed else None, "stars_of_this_rank": int(len(mine)),
                             # this rank's shard by phase: per-star blocks, start points, burn-in + sampling, summaries (+ D2H)

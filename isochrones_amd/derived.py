@@ -3,7 +3,8 @@ interpolated at every sample by the HIP kernel of libiso_derived.so (``iso_deriv
 include/isochrones_amd_derived.h).  The result is a chain of its own in the sampler's parameter-major layout, so the
 quantile kernel summarises it where it lies.
 
-Model-grid columns only: band magnitudes go through the bolometric-correction grid and are not served here."""
+Model-grid columns only: band magnitudes go through the bolometric-correction grid and are served by
+:mod:`isochrones_amd.predictive` (libiso_predict.so)."""
 from __future__ import annotations
 
 import ctypes as C

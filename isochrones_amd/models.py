@@ -203,6 +203,7 @@ class ModelGridInterpolator:
         self._eep_handles.release()
         self.__dict__.pop("_solve_tables", None)
         self.__dict__.pop("_derived_tables", None)
+        self.__dict__.pop("_predict_tables", None)
 
     def __del__(self):
         try:

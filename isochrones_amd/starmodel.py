@@ -959,9 +959,29 @@ class BasicStarModel(_NestedFitMixin, _ConvenienceMixin, _DeviceModelMixin):
             return cols + list(self.props)
         return cols + [p if p in self.derived_samples.columns else "{}_0".format(p) for p in self.props]
 
+    def _device_predictive(self):
+        """The posterior-predictive kernel's result on the device sampler's stored chain (``FusedEnsembleSampler.predictive``),
+        or None where it does not apply: no MCMC fit by the device-resident sampler, no band, or an observed property other
+        than Teff, logg, feh and parallax."""
+        from .predictive import SPEC_TERMS
+        from .sampler import FusedEnsembleSampler
+        smp = getattr(self, "_sampler", None)
+        if (getattr(self, "_fit_kind", "mcmc") != "mcmc" or not isinstance(smp, FusedEnsembleSampler) or smp._stacked
+                or smp._chain is None or not self.bands or any(p not in SPEC_TERMS for p in self.props)):
+            return None
+        cached = getattr(self, "_predictive", None)
+        if cached is None or cached[0] is not smp._chain:
+            obs = {k: self.kwargs[k] for k in list(self.bands) + list(self.props)}
+            cached = self._predictive = (smp._chain, smp.predictive(self.ic, obs, bands=tuple(self.bands), N=self.N))
+        return cached[1]
+
     @property
     def posterior_predictive(self):
-        """Mean chi^2 per observable of the derived samples against the observations."""
+        """Mean chi^2 per observable of the derived samples against the observations (reference starmodel.py:1828-1836).
+        After an MCMC fit by the device-resident sampler: the ``ppc`` of the libiso_predict.so kernel on the stored chain."""
+        pp = self._device_predictive()
+        if pp is not None:
+            return float(pp["ppc"])
         d = self.derived_samples
         chisq = 0
         for b in self.bands:
@@ -974,6 +994,11 @@ class BasicStarModel(_NestedFitMixin, _ConvenienceMixin, _DeviceModelMixin):
 
     @property
     def map_pars(self):
+        """The sample with the largest ``lnprob`` (reference starmodel.py:1839-1841); after an MCMC fit by the
+        device-resident sampler it is the kernel's argmax over the stored chain."""
+        pp = self._device_predictive()
+        if pp is not None:
+            return pp["map_pars"].cpu().numpy()
         s = self.samples
         return s.loc[s["lnprob"].idxmax(), list(self.param_names)].values.astype(float)
 
