@@ -1,12 +1,11 @@
 """ctypes binding of the C ABI declared in include/isochrones_amd_predict.h (libiso_predict.so, the posterior-predictive
-check of a stored chain).  Like :func:`isochrones_amd._cabi.lib`, torch is imported before the library is opened, so that every
-library binds to the HIP runtime torch bundles.  There is no fallback: a missing library raises."""
+check of a stored chain); loaded by :mod:`isochrones_amd._sidelib`."""
 from __future__ import annotations
 
 import ctypes as C
-import os
 
-from ._cabi import IsoError
+from ._cabi import IsoError  # noqa: F401  (callers catch it as _predict_cabi.IsoError)
+from ._sidelib import SideLibrary
 
 ERR_INVALID = -1
 ERR_HIP = -2
@@ -15,8 +14,6 @@ MAX_COMPS = 3
 NSPEC = 4
 LANES = 128
 EXPORTED_SYMBOLS = ("iso_predict_version", "iso_predict_last_error", "iso_predict_chain", "iso_predict_chain_host")
-
-_LIB = None
 
 
 class IsoPredictModelTable(C.Structure):
@@ -38,40 +35,13 @@ class IsoPredictOut(C.Structure):
                 ("map_index", C.c_void_p), ("map_pars", C.c_void_p), ("mag_nan", C.c_void_p)]
 
 
-def library_path() -> str:
-    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libiso_predict.so")
-
-
-def lib():
-    """Load (once) and return libiso_predict.so with argtypes set."""
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    path = library_path()
-    if not os.path.exists(path):
-        raise IsoError("isochrones_amd: posterior-predictive library not found at %s - build it with "
-                       "`python -c 'import __graft_entry__ as g; g.build()'` (there is no fallback)" % path)
-    try:
-        import torch  # noqa: F401
-    except Exception:  # pragma: no cover
-        pass
-    L = C.CDLL(path)
+def _declare(L):
     vp, i32 = C.c_void_p, C.c_int32
-    L.iso_predict_version.restype = C.c_char_p
-    L.iso_predict_version.argtypes = []
-    L.iso_predict_last_error.restype = C.c_char_p
-    L.iso_predict_last_error.argtypes = []
     for fn in (L.iso_predict_chain, L.iso_predict_chain_host):
         fn.restype = C.c_int
         fn.argtypes = [C.POINTER(IsoPredictModelTable), C.POINTER(IsoPredictBcTable), vp, vp, C.c_int, C.c_int64, i32, i32,
                        i32, i32, i32, C.POINTER(i32), i32, i32, i32, vp, vp, C.POINTER(IsoPredictOut), vp]
-    _LIB = L
-    return L
 
 
-def check(rc: int):
-    if rc != 0:
-        msg = lib().iso_predict_last_error()
-        e = IsoError("isochrones_amd predict C-ABI error %d: %s" % (rc, (msg or b"").decode()))
-        e.rc = rc
-        raise e
+_SIDE = SideLibrary("predict", "posterior-predictive", _declare)
+library_path, lib, check = _SIDE.library_path, _SIDE.lib, _SIDE.check

@@ -54,6 +54,12 @@ def hipcc() -> str:
     raise RuntimeError("hipcc not found")
 
 
+def max_jobs() -> int:
+    """Worker threads of a build: MAX_JOBS when it is set (a job on a shared host may own far fewer CPUs than the host
+    has), every CPU otherwise."""
+    return max(1, int(os.environ.get("MAX_JOBS") or os.cpu_count() or 2))
+
+
 def _newer(target, deps):
     if not os.path.exists(target):
         return True
@@ -238,7 +244,7 @@ def build(force: bool = False, verbose: bool = False, gate: bool = True) -> str:
         return p.returncode
 
     if jobs:
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 2)) as ex:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), max_jobs())) as ex:
             for rc in ex.map(compile_one, jobs):
                 if rc != 0:
                     raise RuntimeError("hipcc failed")
@@ -282,7 +288,7 @@ def build(force: bool = False, verbose: bool = False, gate: bool = True) -> str:
         sys.stderr.write("WARNING: ISOCHRONES_AMD_ISA_GATE=skip - the generated code was not scanned\n")
         faults = []
     else:
-        with ThreadPoolExecutor(max_workers=os.cpu_count() or 2) as ex:
+        with ThreadPoolExecutor(max_workers=max_jobs()) as ex:
             faults = [tuple(r) for found in ex.map(isa_of, objs) for r in found]
     if faults:
         msg = I.render(faults)

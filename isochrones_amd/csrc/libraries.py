@@ -1,0 +1,102 @@
+"""The side libraries, each a spec for sidelib.KernelLibrary, in the order __graft_entry__.build() builds them.
+
+    python -m isochrones_amd.csrc.libraries NAME [--force] [--verbose]
+
+A new library is one more spec here (and its name in ALL), its sources in csrc/<name>/ and its header
+include/isochrones_amd_<name>.h."""
+from __future__ import annotations
+
+import sys
+
+from .sidelib import INCLUDE, KernelLibrary
+
+_COMMON = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math")
+#: what five of the six are built with.  -ffp-contract=off: the compiler fuses no multiply-add on its own (each spec says
+#: what that buys)
+_NO_CONTRACT = _COMMON + ("-ffp-contract=off", "-Wall", "-Wno-unused-function", "-I" + INCLUDE)
+
+# the star-cluster likelihood (csrc/cluster/)
+# -ffp-contract=off: every product and sum is rounded as written, in the reference's order (no fused multiply-adds), so that
+# the kernel's cells follow the reference's arithmetic as closely as its libm calls allow
+CLUSTER = KernelLibrary(
+    name="cluster", flags=_NO_CONTRACT,
+    #: every kernel the library compiles (tests/test_cluster_library.py pins this set)
+    kernels=("k_cluster_finish", "k_cluster_pairs"),
+    max_vgpr=256, min_waves=2)
+
+# nested sampling of a catalog (csrc/nested/).  Its kernels include libiso_hip.so's header-only device code
+# (iso_fast_kernel.h: lnpost_wave and what it needs), so those headers are part of its source digest.
+# (the flags libiso_hip.so's fused kernels are built with: lnpost_wave is the same code here and there)
+#: (parametrisation, stars per system) of every kernel family; each has the instantiations for 1 .. 12 bands
+_NESTED_FAMILIES = ((0, 1), (1, 1), (1, 2), (1, 3))
+NESTED = KernelLibrary(
+    name="nested",
+    flags=_COMMON + ("-Wall", "-Wno-unused-function", "-Wno-bitwise-instead-of-logical", "-mllvm", "-disable-machine-licm",
+                     "-mllvm", "-amdgpu-sched-strategy=max-ilp", "-I" + INCLUDE),
+    #: every kernel the library compiles (tests/test_nested_catalog_cpu.py pins this set)
+    kernels=tuple("k_catalog_nested<%d, %d, %d>" % (kind, ns, nb) for kind, ns in _NESTED_FAMILIES for nb in range(1, 13)),
+    #: bytes of scratch per lane the family may use, as k_catalog_start has a budget in resources.py: a ratchet, set to what
+    #: the worst instantiation needs today.  A workgroup here owns a CU's LDS, so one wave per SIMD runs whatever the registers
+    #: say and the kernel is compiled for 256 VGPRs; at that size only the many-band multiples spill (binary, 12 bands: 8 B;
+    #: triple, 10 / 11 / 12 bands: 8 / 68 / 148 B), every other instantiation nothing.
+    scratch_budget=(("k_catalog_nested", 148),),
+    max_vgpr=256, min_waves=2,
+    extra_headers=("iso_fast_kernel.h", "iso_internal.h", "../../include/isochrones_amd.h", "fast/*.h"),
+    strip_prefix="nestk::")
+
+# the exact (mass, age, [Fe/H]) -> EEP solve (csrc/solve/)
+# -ffp-contract=off: every product and sum is rounded as written (no fused multiply-adds), so that g(k) is the interpolator's
+# value bit for bit and stays nondecreasing in k, which the bisection rests on
+SOLVE = KernelLibrary(
+    name="solve", flags=_NO_CONTRACT,
+    #: every kernel the library compiles (tests/test_solve_library.py pins this set)
+    kernels=("k_solve_last_axis",),
+    #: the kernel is a chain of dependent gathers: its throughput is occupancy, so the register budget is the 8-waves-per-SIMD
+    #: one, 64 VGPRs; the wave gate itself is the two per SIMD every library has at least
+    max_vgpr=64, min_waves=2)
+
+# per-star chain convergence diagnostics (csrc/diag/)
+# -ffp-contract=off: the compiler fuses nothing on its own; the kernel's fused multiply-adds are the ones written as fma(),
+# which is part of the documented summation order (a pair's row is bit-identical alone or in any batch)
+DIAG = KernelLibrary(
+    name="diag", flags=_NO_CONTRACT,
+    #: every kernel the library compiles (tests/test_diag_library.py pins this set)
+    kernels=("k_diag_chain",),
+    #: k_diag_chain compiles to 44 VGPRs, no scratch and 8 waves per SIMD.  Its inner loop is two LDS reads per multiply-add,
+    #: hidden by the other wavefronts of the CU, so the budget is the 8-waves-per-SIMD one: 64 VGPRs, and no scratch at all
+    max_vgpr=64, min_waves=8)
+
+# model-grid columns along a stored chain (csrc/derived/)
+# -ffp-contract=off: the compiler fuses nothing, and the sources write no fma(): every product and every sum of the header's
+# definition is rounded on its own (a sample's values are bit-identical in any batch, ensemble range and layout)
+DERIVED = KernelLibrary(
+    name="derived", flags=_NO_CONTRACT,
+    #: every kernel the library compiles (tests/test_derived_library.py pins this set)
+    kernels=("k_derived_chain",),
+    #: k_derived_chain compiles to 118 VGPRs, no scratch and 4 waves per SIMD: the eight-column branch keeps 8 accumulators and
+    #: the cell's corner loads in flight (16 two-double loads a sample; they are what hides the gather latency).  Forcing 8 waves
+    #: (64 VGPRs) spills to scratch, so the budget is the 4-waves-per-SIMD one: 128 VGPRs, and no scratch at all
+    max_vgpr=128, min_waves=4)
+
+# the posterior-predictive check of a stored chain (csrc/predict/)
+# -ffp-contract=off: the compiler fuses nothing, and the sources write no fma(): every product and every sum of the header's
+# definition is rounded on its own (a sample's values are bit-identical in any batch, ensemble range and layout)
+PREDICT = KernelLibrary(
+    name="predict", flags=_NO_CONTRACT,
+    #: every kernel the library compiles (tests/test_predict_library.py pins this set)
+    kernels=("k_predict_chain",),
+    #: k_predict_chain compiles to 239 VGPRs, no scratch and 2 waves per SIMD.  A sample holds the brackets and weights of a 4-D
+    #: cell, eight band accumulators, four corners of eight bands in flight and the model cell's 32 values; the call's 60-odd
+    #: uniform values (two tables, strides, outputs) are staged in LDS because as kernel arguments they overflow the SGPR file and
+    #: their spill slots count as scratch.  The workgroup is two waves, so the budget is the 2-waves-per-SIMD one: 256 VGPRs
+    max_vgpr=256, min_waves=2)
+
+ALL = (CLUSTER, NESTED, SOLVE, DIAG, DERIVED, PREDICT)
+
+
+if __name__ == "__main__":
+    by_name = {spec.name: spec for spec in ALL}
+    names = [a for a in sys.argv[1:] if not a.startswith("--")]
+    if len(names) != 1 or names[0] not in by_name:
+        sys.exit("usage: python -m isochrones_amd.csrc.libraries {%s} [--force] [--verbose]" % ",".join(by_name))
+    print(by_name[names[0]].build(force="--force" in sys.argv, verbose="--verbose" in sys.argv))

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from isochrones_amd.csrc import build_cluster as B
+from isochrones_amd.csrc.libraries import CLUSTER as B
 
 from . import _cluster_hp as H
 from . import _cluster_ref as R

@@ -4,7 +4,7 @@ import ctypes
 import os
 import re
 
-from isochrones_amd.csrc import build_cluster as B
+from isochrones_amd.csrc.libraries import CLUSTER as B
 from isochrones_amd.csrc import isa_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -41,9 +41,3 @@ def test_resources_and_kernel_set():
 def test_generated_code_is_clean():
     path = _built()
     assert isa_check.scan_library(path, jobs=1) == []
-
-
-def test_the_main_library_is_not_touched():
-    from isochrones_amd.csrc import build as main
-    assert not any("cluster" in s for s in main.sources())
-    assert B.OBJDIR != main.OBJDIR and B.RESOURCES != main.RESOURCES and B.STAMP != main.STAMP

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from isochrones_amd import _cabi, _derived_cabi
-from isochrones_amd.csrc import build_derived
+from isochrones_amd.csrc.libraries import DERIVED as build_derived
 from tests import _derived_twin as tw
 
 

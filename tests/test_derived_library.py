@@ -1,10 +1,10 @@
 """libiso_derived.so (model-grid columns along a stored chain) builds for gfx950 without a GPU, exports its C ABI and
-passes its gates: no AGPRs, no scratch, the register budget of build_derived, its waves per SIMD, a clean isa_check scan."""
+passes its gates: no AGPRs, no scratch, the register budget of libraries.DERIVED, its waves per SIMD, a clean isa_check scan."""
 import ctypes
 import os
 import re
 
-from isochrones_amd.csrc import build_derived as B
+from isochrones_amd.csrc.libraries import DERIVED as B
 from isochrones_amd.csrc import isa_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -59,11 +59,3 @@ def test_resources_and_kernel_set():
 def test_generated_code_is_clean():
     path = _built()
     assert isa_check.scan_library(path, jobs=1) == []
-
-
-def test_the_other_libraries_are_not_touched():
-    from isochrones_amd.csrc import build as main, build_cluster, build_diag, build_nested, build_solve
-    assert not any("derived" in os.path.basename(s) for s in main.sources())
-    for other in (main, build_cluster, build_nested, build_solve, build_diag):
-        assert B.OBJDIR != other.OBJDIR and B.RESOURCES != other.RESOURCES and B.STAMP != other.STAMP and B.OUT != other.OUT
-        assert not set(B.sources()) & set(other.sources())

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from isochrones_amd import _cabi, _diag_cabi
-from isochrones_amd.csrc import build_diag
+from isochrones_amd.csrc.libraries import DIAG as build_diag
 from tests import _diag_twin as tw
 
 

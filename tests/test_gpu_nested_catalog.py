@@ -367,7 +367,7 @@ def test_select_multiplicity():
 def test_every_instantiation_is_launched_and_replayed():
     """Every (parametrisation, stars, bands) kernel of libiso_nested.so, by name, on a 4-star catalog with 40 live points; the
     first two macro-steps of every fitted star are replayed against the oracle."""
-    from isochrones_amd.csrc import build_nested as B
+    from isochrones_amd.csrc.libraries import NESTED as B
     launched = set()
     seed, nlive = 31, 40
     for nb in range(1, 13):

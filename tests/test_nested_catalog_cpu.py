@@ -125,7 +125,7 @@ def test_star_index_keying_is_independent_of_the_batch():
 
 # ---- 4. the library ----
 def _built():
-    from isochrones_amd.csrc import build_nested as B
+    from isochrones_amd.csrc.libraries import NESTED as B
     path = B.build()
     assert os.path.exists(path) and B.up_to_date()
     return path
@@ -143,7 +143,7 @@ def test_library_header_symbols_are_exported():
 
 
 def test_library_kernel_set_and_gates():
-    from isochrones_amd.csrc import build_nested as B
+    from isochrones_amd.csrc.libraries import NESTED as B
     _built()
     table = B.resource_table()
     want = {"k_catalog_nested<%d, %d, %d>" % (kind, ns, nb) for kind, ns in ((0, 1), (1, 1), (1, 2), (1, 3)) for nb in range(1, 13)}
@@ -157,7 +157,8 @@ def test_library_kernel_set_and_gates():
 
 
 def test_library_generated_code_is_clean_and_the_main_library_untouched():
-    from isochrones_amd.csrc import build_nested as B, build as main, isa_check
+    from isochrones_amd.csrc import build as main, isa_check
+    from isochrones_amd.csrc.libraries import NESTED as B
     path = _built()
     assert isa_check.scan_library(path, jobs=1) == []
     assert not any("nested" in os.path.basename(s) for s in main.sources())

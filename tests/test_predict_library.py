@@ -1,10 +1,10 @@
 """libiso_predict.so (posterior-predictive check of a stored chain) builds for gfx950 without a GPU, exports its C ABI and
-passes its gates: no AGPRs, no scratch, the register budget of build_predict, its waves per SIMD, a clean isa_check scan."""
+passes its gates: no AGPRs, no scratch, the register budget of libraries.PREDICT, its waves per SIMD, a clean isa_check scan."""
 import ctypes
 import os
 import re
 
-from isochrones_amd.csrc import build_predict as B
+from isochrones_amd.csrc.libraries import PREDICT as B
 from isochrones_amd.csrc import isa_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -61,11 +61,3 @@ def test_resources_and_kernel_set():
 
 def test_generated_code_is_clean():
     assert isa_check.scan_library(_built(), jobs=1) == []
-
-
-def test_the_other_libraries_are_not_touched():
-    from isochrones_amd.csrc import build as main, build_cluster, build_derived, build_diag, build_nested, build_solve
-    for other in (main, build_cluster, build_nested, build_solve, build_diag, build_derived):
-        assert B.OBJDIR != other.OBJDIR and B.RESOURCES != other.RESOURCES and B.STAMP != other.STAMP and B.OUT != other.OUT
-        assert not set(B.sources()) & set(other.sources())
-    assert set(build_derived.KERNELS) == {"k_derived_chain"}

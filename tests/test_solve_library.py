@@ -1,12 +1,12 @@
 """libiso_solve.so (the exact (mass, age, [Fe/H]) -> EEP solve) builds for gfx950 without a GPU, exports its C ABI and
-passes its gates: no AGPRs, no scratch, the register budget of build_solve, at least two waves per SIMD, a clean isa_check
+passes its gates: no AGPRs, no scratch, the register budget of libraries.SOLVE, at least two waves per SIMD, a clean isa_check
 scan, and no scalar-memory write in its sources."""
 import ctypes
 import glob
 import os
 import re
 
-from isochrones_amd.csrc import build_solve as B
+from isochrones_amd.csrc.libraries import SOLVE as B
 from isochrones_amd.csrc import isa_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -69,9 +69,3 @@ def test_sources_hold_no_scalar_memory_write():
     for f in files:
         text = open(f).read().lower()
         assert not any(w in text for w in words), f
-
-
-def test_the_main_library_is_not_touched():
-    from isochrones_amd.csrc import build as main
-    assert not any("solve" in os.path.basename(s) for s in main.sources())
-    assert B.OBJDIR != main.OBJDIR and B.RESOURCES != main.RESOURCES and B.STAMP != main.STAMP

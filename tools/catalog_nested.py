@@ -30,11 +30,11 @@ def main():
     import torch
     import isochrones_amd as ia
     from isochrones_amd.catalog import fit_stars_nested_gpu, nested_result_columns
-    from isochrones_amd.csrc import build_nested
+    from isochrones_amd.csrc.libraries import NESTED
     bands = ["G", "BP", "RP"]
     ic = ia.synthetic_track(bands=bands)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    table = build_nested.resource_table()
+    table = NESTED.resource_table()
     res = table["k_catalog_nested<0, 1, 3>"]
     cols = nested_result_columns(ic.param_names)
     i_ncall, i_niter, i_err = cols.index("ncall"), cols.index("niter"), cols.index("lnZ_err")
