@@ -24,6 +24,7 @@ import os
 import numpy as np
 
 from . import _cabi, device as dev
+from .derived import fit_param_names as _catalog_param_names
 from .starmodel import BasicStarModel
 
 
@@ -535,6 +536,37 @@ def result_columns(param_names, diagnostics=False, derived=(), predictive=()):
     return cols + ["ok"]
 
 
+def result_blocks(cols, param_names, diagnostics=False, derived=(), predictive=()):
+    """``{block: slice}`` into ``cols`` = ``result_columns(param_names, diagnostics, derived, predictive)``, each block found by
+    the name of its first column: what ``fit_stars_gpu`` writes with one assignment each (a further block: one more entry)."""
+    D, first = len(param_names), param_names[0]
+    blocks = [("quantiles", first + "_median", 3 * D), ("lnpost_max", "lnpost_max", 1), ("acceptance", "acceptance", 1)]
+    if diagnostics:
+        blocks += [("diag", first + "_tau", 3 * D)] + [(name, name, 1) for name in DIAG_TAIL]
+    if derived:
+        blocks += [("derived", derived[0] + "_median", 3 * len(derived))]
+    if predictive:
+        nb = len(predictive)
+        blocks += [("ppc", "ppc", 1), ("ppc_nbad", "ppc_nbad", 1), ("mag_quantiles", predictive[0] + "_mag_median", 3 * nb),
+                   ("term_chi2", "chi2_" + predictive[0], nb + 4), ("map_pars", "map_" + first, D)]
+    blocks += [("ok", "ok", 1)]
+    return {block: slice(cols.index(name), cols.index(name) + width) for block, name, width in blocks}
+
+
+def _timer(timings):
+    """``mark(name)``: with a ``timings`` dict, wait for the device and add the time since the last mark to ``timings[name]``."""
+    import time
+    last = [time.perf_counter()]
+    def mark(name):
+        if timings is not None:
+            import torch
+            torch.cuda.synchronize()
+            now = time.perf_counter()
+            timings[name] = timings.get(name, 0.0) + now - last[0]
+            last[0] = now
+    return mark
+
+
 def _predictive_bands(catalog, ic):
     """The bands a posterior-predictive check of this catalog's fits compares: the catalog's that the BC grid has, in the
     catalog's order (the order of a fit's magnitude columns)."""
@@ -570,29 +602,20 @@ def fit_stars_gpu(catalog: StarCatalog, ic, indices, N=1, nwalkers=32, nburn=150
     filled with what a move-by-move replay of the SAMPLING run needs - the ensembles as burn-in left them (``pos`` [S, W, D],
     ``lnp`` [S, W]), the sampler's ``seed``, the step counter the run starts at (``step0`` = nburn), the start points."""
     import torch
-    import time as _time
-
-    def _mark(name, _t=[_time.perf_counter()]):
-        if timings is not None:
-            torch.cuda.synchronize()
-            now = _time.perf_counter()
-            timings[name] = timings.get(name, 0.0) + now - _t[0]
-            _t[0] = now
-
+    _mark = _timer(timings)
     if diagnostics and not fused:
         raise ValueError("diagnostics=True needs the fused sampler (its stored chain is what the diagnostics kernel reads)")
     derived_props, derived_labels = _derived_request(ic, derived, N)
     if derived_props and not fused:
         raise ValueError("derived needs the fused sampler (its stored chain is what the derived-properties kernel reads)")
-    n_diag = 3 * (N + 4) + 3 if diagnostics else 0          # columns between acceptance and ok
-    n_diag += 3 * len(derived_labels)
     if predictive and not fused:
         raise ValueError("predictive needs the fused sampler (its stored chain is what the posterior-predictive kernel reads)")
     pbands = _predictive_bands(catalog, ic) if predictive else ()
-    n_pred = (2 + 3 * len(pbands) + len(pbands) + 4 + (N + 4)) if predictive else 0
-    n_diag += n_pred
+    names = _catalog_param_names(ic, N)
+    cols = result_columns(names, diagnostics, derived_labels, pbands)
+    at = result_blocks(cols, names, diagnostics, derived_labels, pbands)
     if len(indices) == 0:
-        return np.empty((0, 3 * (N + 4) + 3 + n_diag))
+        return np.empty((0, len(cols)))
     if return_chains and (not fused or len(indices) > max_stars_per_batch):
         raise ValueError("return_chains needs the fused sampler and at most max_stars_per_batch stars")
     if len(indices) > max_stars_per_batch:
@@ -622,8 +645,8 @@ def fit_stars_gpu(catalog: StarCatalog, ic, indices, N=1, nwalkers=32, nburn=150
         if not bool(good.any()):
             # no star of the batch found a start point: nothing to sample, every row reports ok = 0
             post.close()
-            out = np.full((post.n_models, 3 * D + 3 + n_diag), np.nan)
-            out[:, -1] = 0.0
+            out = np.full((post.n_models, len(cols)), np.nan)
+            out[:, at["ok"]] = 0.0
             if return_chains:
                 raise ValueError("no star of the batch has a start point with a finite lnpost")
             return out
@@ -686,31 +709,28 @@ def fit_stars_gpu(catalog: StarCatalog, ic, indices, N=1, nwalkers=32, nburn=150
         i1 = torch.clamp(i0 + 1, max=m - 1)
         frac = pick - i0.to(torch.float64)
         q = srt[:, :, i0] * (1 - frac) + srt[:, :, i1] * frac                                   # [S, D, 3] (linear, as np.percentile)
-    rows = torch.empty(post.n_models, 3 * D + 3 + n_diag, dtype=torch.float64, device=q.device)
-    rows[:, : 3 * D] = q.reshape(post.n_models, 3 * D)
+    S = post.n_models
+    rows = torch.empty(S, len(cols), dtype=torch.float64, device=q.device)
+    rows[:, at["quantiles"]] = q.reshape(S, 3 * D)
     if fused:       # storage order is [step][star * W + walker]: reduce over steps first (coalesced), then walkers
-        rows[:, 3 * D] = sampler._lnprob.amax(dim=0).view(post.n_models, nwalkers).amax(dim=1)
+        rows[:, at["lnpost_max"]] = sampler._lnprob.amax(dim=0).view(S, nwalkers).amax(dim=1, keepdim=True)
     else:
-        rows[:, 3 * D] = lnps.amax(dim=(1, 2))
-    rows[:, 3 * D + 1] = acc_frac
+        rows[:, at["lnpost_max"]] = lnps.amax(dim=(1, 2))[:, None]
+    rows[:, at["acceptance"]] = acc_frac[:, None]
     if diagnostics:
-        d0 = 3 * D + 2
-        rows[:, d0: d0 + 3 * D] = torch.stack([dg.tau, dg.ess, dg.rhat], dim=2).reshape(post.n_models, 3 * D)
-        rows[:, d0 + 3 * D] = dg.tau.amax(dim=1)
-        rows[:, d0 + 3 * D + 1] = dg.rhat.amax(dim=1)
-        rows[:, d0 + 3 * D + 2] = dg.window_ok.amin(dim=1)
+        rows[:, at["diag"]] = torch.stack([dg.tau, dg.ess, dg.rhat], dim=2).reshape(S, 3 * D)
+        rows[:, at["tau_max"]] = dg.tau.amax(dim=1, keepdim=True)
+        rows[:, at["rhat_max"]] = dg.rhat.amax(dim=1, keepdim=True)
+        rows[:, at["window_ok"]] = dg.window_ok.amin(dim=1, keepdim=True)
     if derived_props:
-        d1 = rows.shape[1] - 1 - n_pred
-        rows[:, d1 - 3 * len(derived_labels): d1] = dq.reshape(post.n_models, 3 * len(derived_labels))
+        rows[:, at["derived"]] = dq.reshape(S, 3 * len(derived_labels))
     if predictive:
-        p0 = rows.shape[1] - 1 - n_pred
-        nb = len(pbands)
-        rows[:, p0] = pp["ppc"]
-        rows[:, p0 + 1] = pp["n_bad"].to(torch.float64)
-        rows[:, p0 + 2: p0 + 2 + 3 * nb] = pp["mag_quantiles"].reshape(post.n_models, 3 * nb)
-        rows[:, p0 + 2 + 3 * nb: p0 + 2 + 4 * nb + 4] = pp["term_chi2"]
-        rows[:, p0 + 2 + 4 * nb + 4: -1] = pp["map_pars"]
-    rows[:, -1] = good.to(torch.float64)
+        rows[:, at["ppc"]] = pp["ppc"][:, None]
+        rows[:, at["ppc_nbad"]] = pp["n_bad"].to(torch.float64)[:, None]
+        rows[:, at["mag_quantiles"]] = pp["mag_quantiles"].reshape(S, 3 * len(pbands))
+        rows[:, at["term_chi2"]] = pp["term_chi2"]
+        rows[:, at["map_pars"]] = pp["map_pars"]
+    rows[:, at["ok"]] = good.to(torch.float64)[:, None]
     rows[failed, :-1] = float("nan")
     out = rows.cpu().numpy()
     _mark("summaries")
@@ -742,10 +762,6 @@ def nested_result_columns(param_names):
     for p in param_names:
         cols += ["%s_%s" % (p, s) for s in NESTED_STATS]
     return cols + list(NESTED_TAIL)
-
-
-def _catalog_param_names(ic, N):
-    return tuple(ic.param_names) if N == 1 else tuple(["eep_%d" % i for i in range(N)] + list(ic.param_names[1:]))
 
 
 def _nested_fast_args(post):
@@ -787,16 +803,8 @@ def fit_stars_nested_gpu(catalog: StarCatalog, ic, indices, N=1, n_live_points=4
     3 + D + D D] (threshold, first draw examined, last draw consumed, ellipsoid mean and factor), ``n_steps`` [S], and
     ``lo`` / ``hi`` [S, D] - numpy arrays."""
     import torch
-    import time as _time
     from . import _nested_cabi as NC
-
-    def _mark(name, _t=[_time.perf_counter()]):
-        if timings is not None:
-            torch.cuda.synchronize()
-            now = _time.perf_counter()
-            timings[name] = timings.get(name, 0.0) + now - _t[0]
-            _t[0] = now
-
+    _mark = _timer(timings)
     indices = np.asarray(indices, dtype=np.int64)
     D = N + 4
     width = 2 * D + 8

@@ -14,57 +14,32 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include "isochrones_amd_derived.h"
+#include "../common/chain_view.h"
+#include "../common/grid_cell.h"
 
 namespace {
 
 constexpr int BLOCK = 256;
 constexpr int MAX_BLOCKS = 256 * 8;             // a memory-bound stream: eight workgroups per CU, the rest by striding
 constexpr int MAXC = ISO_DERIVED_MAX_COMPS;
-
-thread_local char g_err[256];
-
-int fail(int rc, const char* msg) {
-    snprintf(g_err, sizeof g_err, "%s", msg);
-    return rc;
-}
+static_assert(ISO_DERIVED_ROW_MAJOR == CHAIN_ROW_MAJOR && ISO_DERIVED_PARAM_MAJOR == CHAIN_PARAM_MAJOR, "chain layouts");
 
 struct Args {
     const double* chain;
     double* out;
     int32_t* nan_count;
     iso_derived_table T;
-    int64_t st_t, st_d, st_w;                   // strides of (step, parameter, row) in doubles
+    ChainStrides st;
     int64_t row0;                               // ens_begin * W
     int32_t R, W, C, nsteps;                    // R = n_ens_out * W
     int32_t chunks, items;                      // ceil(R / BLOCK), nsteps * chunks
-    int32_t comp[MAXC];                         // p0 | p1 << 8 | pk << 16 | FRESH01 where (p0, p1) differ from the
-};                                              // component before (the first component: always)
+    int32_t comp[MAXC];                         // pack_comp() | FRESH01 where (p0, p1) differ from the component
+};                                              // before (the first component: always)
 
 constexpr int FRESH01 = 1 << 24;
-
-// i = the largest index with ax[i] <= x, at most n - 2; t = (x - ax[i]) / (ax[i + 1] - ax[i]).  Stays inside the axis for
-// every x (a NaN compares false everywhere: i = 0); the caller has decided whether x is on the axis at all.
-__host__ __device__ inline void bracket(const double* __restrict__ ax, int n, double x, int& i, double& t) {
-    int base = 0, len = n;
-    while (len > 1) {
-        const int half = len >> 1;
-        base = (ax[base + half] <= x) ? base + half : base;
-        len -= half;
-    }
-    base = base < n - 2 ? base : n - 2;
-    const double lo = ax[base], hi = ax[base + 1];
-    i = base;
-    t = (x - lo) / (hi - lo);
-}
-
-// NaN first, then the bounds test, as the interpolator
-__host__ __device__ inline bool on_axis(const double* __restrict__ ax, int n, double x) {
-    return x == x && !(x < ax[0]) && !(x > ax[n - 1]);
-}
 
 template <int Q>
 __device__ __forceinline__ void corner(const double* __restrict__ p, double w, double (&v)[Q]) {
@@ -91,7 +66,7 @@ __device__ __forceinline__ void derive(const Args& A) {
         const int t = item / A.chunks;
         const int r = (item - t * A.chunks) * BLOCK + (int)threadIdx.x;
         if (r >= R) continue;
-        const double* __restrict__ row = A.chain + (int64_t)t * A.st_t + (A.row0 + r) * A.st_w;
+        const double* __restrict__ row = A.chain + (int64_t)t * A.st.st_t + (A.row0 + r) * A.st.st_w;
         double* __restrict__ o = A.out + (int64_t)t * CQ * R + r;
         int i0 = 0, i1 = 0;
         double t0 = 0.0, t1 = 0.0;
@@ -100,12 +75,12 @@ __device__ __forceinline__ void derive(const Args& A) {
             const int comp = c == 0 ? A.comp[0] : (c == 1 ? A.comp[1] : A.comp[2]);      // wave-uniform
             // the first two axes: once for every run of components that read them from the same parameters
             if (comp & FRESH01) {
-                const double x0 = row[(comp & 255) * A.st_d], x1 = row[((comp >> 8) & 255) * A.st_d];
+                const double x0 = row[comp_p0(comp) * A.st.st_d], x1 = row[comp_p1(comp) * A.st.st_d];
                 ok01 = on_axis(T.ax0, T.n0, x0) && on_axis(T.ax1, T.n1, x1);
                 bracket(T.ax0, T.n0, x0, i0, t0);
                 bracket(T.ax1, T.n1, x1, i1, t1);
             }
-            const double xk = row[((comp >> 16) & 255) * A.st_d];
+            const double xk = row[comp_pk(comp) * A.st.st_d];
             const bool ok = ok01 && on_axis(T.axk, T.nk, xk);
             double v[Q];
             if (ok) {
@@ -126,7 +101,7 @@ __device__ __forceinline__ void derive(const Args& A) {
                 corner<Q>(p + s0 + s1 + sk, (t0 * t1) * tk, v);
             } else {
 #pragma unroll
-                for (int j = 0; j < Q; ++j) v[j] = __longlong_as_double(0x7ff8000000000000LL);
+                for (int j = 0; j < Q; ++j) v[j] = qnan();
             }
             bool any = false;
 #pragma unroll
@@ -161,25 +136,20 @@ __global__ void __launch_bounds__(BLOCK) k_derived_chain(const Args A) {
 int prepare(const char* who, bool device, const iso_derived_table* t, const double* chain, int layout, int64_t nsteps,
             int32_t n_ens, int32_t W, int32_t ndim, int32_t ens_begin, int32_t n_ens_out, const int32_t* comps, int32_t C,
             double* out, int32_t* nan_count, Args& A) {
-    char buf[220];
+    const ChainShape s{layout, nsteps, n_ens, W, ndim, ens_begin, n_ens_out, comps, C};
     const char* why = nullptr;
     if (!t || !t->cols || !t->ax0 || !t->ax1 || !t->axk) why = "null table pointer";
     else if (!chain || !out || !nan_count || !comps) why = "null pointer";
-    else if (layout != ISO_DERIVED_ROW_MAJOR && layout != ISO_DERIVED_PARAM_MAJOR) why = "unknown chain layout";
-    else if (nsteps < 1 || n_ens < 1 || W < 1 || ndim < 1) why = "nsteps, n_ens, W and ndim must be at least 1";
+    else if ((why = chain_shape_error(CHAIN_CHECK_LAYOUT | CHAIN_CHECK_SIZES, s))) {}
     else if (t->Q < 1 || t->Q > ISO_DERIVED_MAX_COLS) why = "Q must be 1 to 8 columns per call";
     else if (C < 1 || C > ISO_DERIVED_MAX_COMPS) why = "C must be 1 to 3 components";
     else if (t->n0 < 2 || t->n1 < 2 || t->nk < 2) why = "every axis needs at least 2 nodes";
     else if ((int64_t)t->n0 * t->n1 * t->nk * t->Q > INT32_MAX) why = "table too large (more than 2^31 - 1 entries)";
-    else if (ens_begin < 0 || n_ens_out < 1 || (int64_t)ens_begin + n_ens_out > n_ens)
-        why = "ensemble range [ens_begin, ens_begin + n_ens_out) must be non-empty and inside [0, n_ens)";
-    else if ((int64_t)n_ens * W > INT32_MAX) why = "more than 2^31 - 1 rows (split the batch)";
+    else if ((why = chain_shape_error(CHAIN_CHECK_RANGE | CHAIN_CHECK_ROWS, s))) {}
     else if (nsteps > INT32_MAX) why = "nsteps beyond 2^31 - 1";
     else if (ndim > 256) why = "more than 256 parameters";
     else if (device && t->Q % 2 == 0 && ((uintptr_t)t->cols & 15)) why = "cols must be 16-byte aligned for an even Q";
-    if (!why)
-        for (int c = 0; c < C * 3; ++c)
-            if (comps[c] < 0 || comps[c] >= ndim) why = "a component's parameter index is outside [0, ndim)";
+    else why = chain_shape_error(CHAIN_CHECK_COMPS, s);
     if (!why) {
         const int64_t R = (int64_t)n_ens_out * W, chunks = (R + BLOCK - 1) / BLOCK;
         if (nsteps * chunks > INT32_MAX) why = "too many samples in one call (split the ensemble range)";
@@ -187,20 +157,8 @@ int prepare(const char* who, bool device, const iso_derived_table* t, const doub
         A.chunks = (int32_t)chunks;
         A.items = (int32_t)(nsteps * chunks);
     }
-    if (why) {
-        snprintf(buf, sizeof buf, "%s: %s", who, why);
-        return fail(ISO_DERIVED_ERR_INVALID, buf);
-    }
-    const int64_t rows = (int64_t)n_ens * W;
-    if (layout == ISO_DERIVED_PARAM_MAJOR) {
-        A.st_t = (int64_t)ndim * rows;
-        A.st_d = rows;
-        A.st_w = 1;
-    } else {
-        A.st_t = rows * ndim;
-        A.st_d = 1;
-        A.st_w = ndim;
-    }
+    if (why) return fail(ISO_DERIVED_ERR_INVALID, who, why);
+    A.st = chain_strides(layout, (int64_t)n_ens * W, ndim);
     A.chain = chain;
     A.out = out;
     A.nan_count = nan_count;
@@ -213,7 +171,7 @@ int prepare(const char* who, bool device, const iso_derived_table* t, const doub
         A.comp[c] = 0;
         if (c >= C) continue;
         const bool fresh = c == 0 || comps[3 * c] != comps[3 * c - 3] || comps[3 * c + 1] != comps[3 * c - 2];
-        A.comp[c] = comps[3 * c] | comps[3 * c + 1] << 8 | comps[3 * c + 2] << 16 | (fresh ? FRESH01 : 0);
+        A.comp[c] = pack_comp(comps[3 * c], comps[3 * c + 1], comps[3 * c + 2]) | (fresh ? FRESH01 : 0);
     }
     return 0;
 }
@@ -258,11 +216,11 @@ int iso_derived_chain_host(const iso_derived_table* table, const double* chain, 
     memset(nan_count, 0, sizeof(int32_t) * (size_t)n_ens_out * CQ);
     for (int64_t t = 0; t < nsteps; ++t)
         for (int r = 0; r < R; ++r) {
-            const double* row = chain + t * A.st_t + (A.row0 + r) * A.st_w;
+            const double* row = chain + t * A.st.st_t + (A.row0 + r) * A.st.st_w;
             for (int c = 0; c < C; ++c) {
                 const int comp = A.comp[c];
-                const double x0 = row[(comp & 255) * A.st_d], x1 = row[((comp >> 8) & 255) * A.st_d],
-                             xk = row[((comp >> 16) & 255) * A.st_d];
+                const double x0 = row[comp_p0(comp) * A.st.st_d], x1 = row[comp_p1(comp) * A.st.st_d],
+                             xk = row[comp_pk(comp) * A.st.st_d];
                 double v[ISO_DERIVED_MAX_COLS];
                 if (on_axis(T.ax0, T.n0, x0) && on_axis(T.ax1, T.n1, x1) && on_axis(T.axk, T.nk, xk)) {
                     int i[3];
@@ -279,7 +237,7 @@ int iso_derived_chain_host(const iso_derived_table* table, const double* chain, 
                         for (int q = 0; q < Q; ++q) v[q] = v[q] + p[q] * w;
                     }
                 } else {
-                    for (int q = 0; q < Q; ++q) v[q] = NAN;
+                    for (int q = 0; q < Q; ++q) v[q] = qnan();
                 }
                 for (int q = 0; q < Q; ++q) {
                     out[(t * CQ + c * Q + q) * R + r] = v[q];

@@ -14,11 +14,12 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include <vector>
 
 #include "isochrones_amd_diag.h"
+#include "../common/chain_view.h"
+#include "../common/grid_cell.h"
 
 namespace {
 
@@ -30,16 +31,10 @@ constexpr int ITEM_LAGS = 64 * LANE_LAGS;
 constexpr int TILE_WALKERS = 16;                // walkers staged at once when they fit 64 KB
 constexpr size_t LDS_PLAIN = 64 * 1024;         // what a launch gets without asking
 constexpr size_t LDS_LIMIT = 160 * 1024;        // a CU's LDS
-
-thread_local char g_err[256];
-
-int fail(int rc, const char* msg) {
-    snprintf(g_err, sizeof g_err, "%s", msg);
-    return rc;
-}
+static_assert(ISO_DIAG_ROW_MAJOR == CHAIN_ROW_MAJOR && ISO_DIAG_PARAM_MAJOR == CHAIN_PARAM_MAJOR, "chain layouts");
 
 struct Shape {
-    int64_t st_t, st_d, st_w;                   // strides of (step, parameter, row) in doubles
+    ChainStrides st;
     int T, S, W, D, K;
     int WT, Tp;                                 // walkers per tile, LDS row stride
     double c;
@@ -50,8 +45,6 @@ struct Shape {
 size_t lds_doubles(int W, int K, int WT, int Tp) {
     return (size_t)GROUPS * (K + 1) + 4 * (size_t)W + 2 * (size_t)WT + (size_t)WT * Tp;
 }
-
-__device__ __forceinline__ double d_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
 // xor butterfly over the 64 lanes, distances 32 .. 1: every lane ends with the same sum, in a fixed order
 __device__ __forceinline__ double wave_sum(double v) {
@@ -101,7 +94,7 @@ __global__ void __launch_bounds__(BLOCK) k_diag_chain(const double* __restrict__
     double* __restrict__ tile = first + WT;                     // [WT][Tp]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int pair = blockIdx.x, s = pair / P.D, d = pair - s * P.D;
-    const double* __restrict__ base = chain + (int64_t)d * P.st_d + (int64_t)s * W * P.st_w;
+    const double* __restrict__ base = chain + (int64_t)d * P.st.st_d + (int64_t)s * W * P.st.st_w;
     const int n = T / 2;                                        // length of a split chain
 
     for (int i = tid; i < GROUPS * K1; i += BLOCK) A[i] = 0.0;
@@ -112,7 +105,7 @@ __global__ void __launch_bounds__(BLOCK) k_diag_chain(const double* __restrict__
         // stage: consecutive lanes read consecutive walkers of one step (coalesced in the parameter-major layout)
         for (int i = tid; i < wt * T; i += BLOCK) {
             const int t = i / wt, wl = i - t * wt;
-            tile[(size_t)wl * Tp + t] = base[(int64_t)t * P.st_t + (int64_t)(w0 + wl) * P.st_w];
+            tile[(size_t)wl * Tp + t] = base[(int64_t)t * P.st.st_t + (int64_t)(w0 + wl) * P.st.st_w];
         }
         __syncthreads();
         for (int wl = tid; wl < wt; wl += BLOCK) {
@@ -170,7 +163,7 @@ __global__ void __launch_bounds__(BLOCK) k_diag_chain(const double* __restrict__
     if (wave != 0) return;
 
     // split R-hat: fixed-order sums over the 2 W chains by one wavefront
-    double rhat = d_nan();
+    double rhat = qnan();
     if (n >= 2) {
         const int nc = 2 * W;
         double p = 0.0, q = 0.0;
@@ -192,10 +185,10 @@ __global__ void __launch_bounds__(BLOCK) k_diag_chain(const double* __restrict__
 
     double* __restrict__ o = out + (size_t)pair * ISO_DIAG_NOUT;
     if (a0 != a0) {                                             // a NaN in the slab reaches every centred value of its walker
-        for (int i = 0; i < ISO_DIAG_NOUT; ++i) o[i] = d_nan();
+        for (int i = 0; i < ISO_DIAG_NOUT; ++i) o[i] = qnan();
         return;
     }
-    double tau = d_nan(), window = (double)K, ok = 0.0;
+    double tau = qnan(), window = (double)K, ok = 0.0;
     if (a0 != 0.0) {
         double acc = 0.0;                                       // sum of rho(1..M)
         int M = 0;
@@ -219,30 +212,15 @@ __global__ void __launch_bounds__(BLOCK) k_diag_chain(const double* __restrict__
 
 int check_args(const char* who, const double* chain, int layout, int64_t nsteps, int32_t n_ens, int32_t W, int32_t ndim,
                double c, int32_t max_lag, const double* out) {
-    char buf[200];
+    const ChainShape s{layout, nsteps, n_ens, W, ndim};
     const char* why = nullptr;
     if (!chain || !out) why = "null pointer";
-    else if (layout != ISO_DIAG_ROW_MAJOR && layout != ISO_DIAG_PARAM_MAJOR) why = "unknown chain layout";
-    else if (nsteps < 1 || n_ens < 1 || W < 1 || ndim < 1) why = "nsteps, n_ens, W and ndim must be at least 1";
+    else if ((why = chain_shape_error(CHAIN_CHECK_LAYOUT | CHAIN_CHECK_SIZES, s))) {}
     else if (!(c > 0.0) || !isfinite(c)) why = "c must be finite and > 0";
     else if (max_lag < 1) why = "max_lag must be at least 1";
     else if ((int64_t)n_ens * ndim > INT32_MAX) why = "more than 2^31 - 1 (ensemble, parameter) pairs (split the batch)";
-    else if ((int64_t)n_ens * W > INT32_MAX) why = "more than 2^31 - 1 rows (split the batch)";
-    if (!why) return 0;
-    snprintf(buf, sizeof buf, "%s: %s", who, why);
-    return fail(ISO_DIAG_ERR_INVALID, buf);
-}
-
-void strides(int layout, int64_t rows, int32_t ndim, int64_t& st_t, int64_t& st_d, int64_t& st_w) {
-    if (layout == ISO_DIAG_PARAM_MAJOR) {
-        st_t = (int64_t)ndim * rows;
-        st_d = rows;
-        st_w = 1;
-    } else {
-        st_t = rows * ndim;
-        st_d = 1;
-        st_w = ndim;
-    }
+    else why = chain_shape_error(CHAIN_CHECK_ROWS, s);
+    return why ? fail(ISO_DIAG_ERR_INVALID, who, why) : 0;
 }
 
 // the definition on one slab y[w][t] (row stride T), plain ascending loops
@@ -337,7 +315,7 @@ int iso_diag_chain(const double* chain, int layout, int64_t nsteps, int32_t n_en
     if (nsteps > (int64_t)(LDS_LIMIT / sizeof(double)))
         return fail(ISO_DIAG_ERR_INVALID, "iso_diag_chain: nsteps too large for the kernel's LDS staging (thin the chain)");
     Shape P;
-    strides(layout, (int64_t)n_ens * W, ndim, P.st_t, P.st_d, P.st_w);
+    P.st = chain_strides(layout, (int64_t)n_ens * W, ndim);
     P.T = (int)nsteps;
     P.S = n_ens;
     P.W = W;
@@ -377,16 +355,15 @@ int iso_diag_chain_host(const double* chain, int layout, int64_t nsteps, int32_t
     const int rc = check_args("iso_diag_chain_host", chain, layout, nsteps, n_ens, W, ndim, c, max_lag, out);
     if (rc) return rc;
     if (nsteps > INT32_MAX) return fail(ISO_DIAG_ERR_INVALID, "iso_diag_chain_host: nsteps beyond 2^31 - 1");
-    int64_t st_t, st_d, st_w;
-    strides(layout, (int64_t)n_ens * W, ndim, st_t, st_d, st_w);
+    const ChainStrides st = chain_strides(layout, (int64_t)n_ens * W, ndim);
     const int T = (int)nsteps;
     const int K = (int)((nsteps - 1 < max_lag) ? nsteps - 1 : max_lag);
     std::vector<double> y((size_t)W * T);
     for (int s = 0; s < n_ens; ++s)
         for (int d = 0; d < ndim; ++d) {
-            const double* base = chain + (int64_t)d * st_d + (int64_t)s * W * st_w;
+            const double* base = chain + (int64_t)d * st.st_d + (int64_t)s * W * st.st_w;
             for (int w = 0; w < W; ++w)
-                for (int t = 0; t < T; ++t) y[(size_t)w * T + t] = base[(int64_t)t * st_t + (int64_t)w * st_w];
+                for (int t = 0; t < T; ++t) y[(size_t)w * T + t] = base[(int64_t)t * st.st_t + (int64_t)w * st.st_w];
             host_pair(y, T, W, K, c, out + ((size_t)s * ndim + d) * ISO_DIAG_NOUT);
         }
     return 0;

@@ -55,6 +55,9 @@ SOLVE = KernelLibrary(
     #: one, 64 VGPRs; the wave gate itself is the two per SIMD every library has at least
     max_vgpr=64, min_waves=2)
 
+#: shared by the three libraries that post-process a stored chain (internal; named outright: a missing one stops the digest)
+_CHAIN_HEADERS = ("common/grid_cell.h", "common/chain_view.h")
+
 # per-star chain convergence diagnostics (csrc/diag/)
 # -ffp-contract=off: the compiler fuses nothing on its own; the kernel's fused multiply-adds are the ones written as fma(),
 # which is part of the documented summation order (a pair's row is bit-identical alone or in any batch)
@@ -64,7 +67,7 @@ DIAG = KernelLibrary(
     kernels=("k_diag_chain",),
     #: k_diag_chain compiles to 44 VGPRs, no scratch and 8 waves per SIMD.  Its inner loop is two LDS reads per multiply-add,
     #: hidden by the other wavefronts of the CU, so the budget is the 8-waves-per-SIMD one: 64 VGPRs, and no scratch at all
-    max_vgpr=64, min_waves=8)
+    max_vgpr=64, min_waves=8, extra_headers=_CHAIN_HEADERS)
 
 # model-grid columns along a stored chain (csrc/derived/)
 # -ffp-contract=off: the compiler fuses nothing, and the sources write no fma(): every product and every sum of the header's
@@ -76,7 +79,7 @@ DERIVED = KernelLibrary(
     #: k_derived_chain compiles to 118 VGPRs, no scratch and 4 waves per SIMD: the eight-column branch keeps 8 accumulators and
     #: the cell's corner loads in flight (16 two-double loads a sample; they are what hides the gather latency).  Forcing 8 waves
     #: (64 VGPRs) spills to scratch, so the budget is the 4-waves-per-SIMD one: 128 VGPRs, and no scratch at all
-    max_vgpr=128, min_waves=4)
+    max_vgpr=128, min_waves=4, extra_headers=_CHAIN_HEADERS)
 
 # the posterior-predictive check of a stored chain (csrc/predict/)
 # -ffp-contract=off: the compiler fuses nothing, and the sources write no fma(): every product and every sum of the header's
@@ -89,7 +92,7 @@ PREDICT = KernelLibrary(
     #: cell, eight band accumulators, four corners of eight bands in flight and the model cell's 32 values; the call's 60-odd
     #: uniform values (two tables, strides, outputs) are staged in LDS because as kernel arguments they overflow the SGPR file and
     #: their spill slots count as scratch.  The workgroup is two waves, so the budget is the 2-waves-per-SIMD one: 256 VGPRs
-    max_vgpr=256, min_waves=2)
+    max_vgpr=256, min_waves=2, extra_headers=_CHAIN_HEADERS)
 
 ALL = (CLUSTER, NESTED, SOLVE, DIAG, DERIVED, PREDICT)
 

@@ -14,10 +14,11 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include "isochrones_amd_predict.h"
+#include "../common/chain_view.h"
+#include "../common/grid_cell.h"
 
 namespace {
 
@@ -26,13 +27,7 @@ constexpr int MAX_BLOCKS = 256 * 8;
 constexpr int MAXC = ISO_PREDICT_MAX_COMPS;
 constexpr int CH = 8;                           // bands per pass
 constexpr int NSPEC = ISO_PREDICT_NSPEC;
-
-thread_local char g_err[256];
-
-int fail(int rc, const char* msg) {
-    snprintf(g_err, sizeof g_err, "%s", msg);
-    return rc;
-}
+static_assert(ISO_PREDICT_ROW_MAJOR == CHAIN_ROW_MAJOR && ISO_PREDICT_PARAM_MAJOR == CHAIN_PARAM_MAJOR, "chain layouts");
 
 struct Args {
     const double* chain;
@@ -42,39 +37,14 @@ struct Args {
     iso_predict_out O;
     iso_predict_model_table M;
     iso_predict_bc_table T;
-    int64_t st_t, st_d, st_w;                   // strides of (step, parameter, row) in doubles
+    ChainStrides st;
     int64_t rows;                               // n_ens * W
     int32_t W, C, nsteps, ndim, B, i_dist, i_AV, ens_begin, n_ens_out;
     int32_t n;                                  // nsteps * W samples an ensemble
-    int32_t comp[MAXC];                         // p0 | p1 << 8 | pk << 16
+    int32_t comp[MAXC];                         // pack_comp()
 };
 
-__host__ __device__ inline double qnan() {
-    union { uint64_t u; double d; } x;
-    x.u = 0x7ff8000000000000ULL;
-    return x.d;
-}
-
 __host__ __device__ inline bool finite_(double x) { return x - x == 0.0; }
-
-// i = the largest index with ax[i] <= x, at most n - 2; t = (x - ax[i]) / (ax[i + 1] - ax[i]) (isochrones_amd_derived.h)
-__host__ __device__ inline void bracket(const double* __restrict__ ax, int n, double x, int& i, double& t) {
-    int base = 0, len = n;
-    while (len > 1) {
-        const int half = len >> 1;
-        base = (ax[base + half] <= x) ? base + half : base;
-        len -= half;
-    }
-    base = base < n - 2 ? base : n - 2;
-    const double lo = ax[base], hi = ax[base + 1];
-    i = base;
-    t = (x - lo) / (hi - lo);
-}
-
-// NaN first, then the bounds test, as the interpolator
-__host__ __device__ inline bool on_axis(const double* __restrict__ ax, int n, double x) {
-    return x == x && !(x < ax[0]) && !(x > ax[n - 1]);
-}
 
 // step 1 of the header: (Teff, logg, feh, Mbol) at (x0, x1, xk)
 __host__ __device__ inline void model4(const iso_predict_model_table& M, double x0, double x1, double xk, double (&v)[4]) {
@@ -149,8 +119,8 @@ __host__ __device__ inline void sample_chunk(const Args& A, const double* __rest
         for (int j = 0; j < nb; ++j) wk[(CH + j) * ws] = 0.0;
     for (int c = 0; c < A.C; ++c) {
         const int comp = c == 0 ? A.comp[0] : (c == 1 ? A.comp[1] : A.comp[2]);
-        const double x0 = row[(comp & 255) * A.st_d], x1 = row[((comp >> 8) & 255) * A.st_d],
-                     xk = row[((comp >> 16) & 255) * A.st_d];
+        const double x0 = row[comp_p0(comp) * A.st.st_d], x1 = row[comp_p1(comp) * A.st.st_d],
+                     xk = row[comp_pk(comp) * A.st.st_d];
         double v[4], bcv[CH];
         model4(A.M, x0, x1, xk, v);
         bc_chunk(A.T, v[0], v[1], v[2], av, b0, nb, bcv);
@@ -192,8 +162,8 @@ __host__ __device__ inline bool sample(const Args& A, int e, int s, const double
                                        double* __restrict__ wk, int ws, int* __restrict__ nanc) {
     const int t = s / A.W, w = s - t * A.W;
     const int64_t r = (int64_t)e * A.W + w, R = (int64_t)A.n_ens_out * A.W;
-    const double* __restrict__ row = A.chain + (int64_t)t * A.st_t + ((int64_t)A.ens_begin * A.W + r) * A.st_w;
-    const double dist = row[A.i_dist * A.st_d], av = row[A.i_AV * A.st_d];
+    const double* __restrict__ row = A.chain + (int64_t)t * A.st.st_t + ((int64_t)A.ens_begin * A.W + r) * A.st.st_w;
+    const double dist = row[A.i_dist * A.st.st_d], av = row[A.i_AV * A.st.st_d];
     bool bad = false;
     double spec[3] = {0.0, 0.0, 0.0};
     for (int b0 = 0; b0 < A.B; b0 += CH) {
@@ -322,9 +292,9 @@ __global__ void __launch_bounds__(BLOCK) k_predict_chain(const Args A_) {
             if (A.O.map_pars) {
                 const int t = best < 0 ? 0 : (int)(best / A.W), w = best < 0 ? 0 : (int)(best - (int64_t)t * A.W);
                 const double* __restrict__ row =
-                    A.chain + (int64_t)t * A.st_t + ((int64_t)(A.ens_begin + e) * A.W + w) * A.st_w;
+                    A.chain + (int64_t)t * A.st.st_t + ((int64_t)(A.ens_begin + e) * A.W + w) * A.st.st_w;
                 for (int d = lane; d < A.ndim; d += BLOCK)
-                    A.O.map_pars[(int64_t)e * A.ndim + d] = best < 0 ? qnan() : row[d * A.st_d];
+                    A.O.map_pars[(int64_t)e * A.ndim + d] = best < 0 ? qnan() : row[d * A.st.st_d];
             }
         }
         __syncthreads();                                        // the next ensemble reuses the LDS
@@ -338,13 +308,12 @@ int prepare(const char* who, const iso_predict_model_table* m, const iso_predict
             const double* lnprob, int layout, int64_t nsteps, int32_t n_ens, int32_t W, int32_t ndim, int32_t ens_begin,
             int32_t n_ens_out, const int32_t* comps, int32_t C, int32_t i_dist, int32_t i_AV, const double* obs_val,
             const double* obs_unc, const iso_predict_out* out, Args& A) {
-    char buf[220];
+    const ChainShape s{layout, nsteps, n_ens, W, ndim, ens_begin, n_ens_out, comps, C};
     const char* why = nullptr;
     if (!m || !m->cols || !m->ax0 || !m->ax1 || !m->axk) why = "null model table pointer";
     else if (!bc || !bc->bc || !bc->axT || !bc->axg || !bc->axf || !bc->axA) why = "null BC table pointer";
     else if (!chain || !comps || !obs_val || !obs_unc || !out) why = "null pointer";
-    else if (layout != ISO_PREDICT_ROW_MAJOR && layout != ISO_PREDICT_PARAM_MAJOR) why = "unknown chain layout";
-    else if (nsteps < 1 || n_ens < 1 || W < 1 || ndim < 1) why = "nsteps, n_ens, W and ndim must be at least 1";
+    else if ((why = chain_shape_error(CHAIN_CHECK_LAYOUT | CHAIN_CHECK_SIZES, s))) {}
     else if (bc->B < 1 || bc->B > ISO_PREDICT_MAX_BANDS) why = "B must be 1 to 32 bands";
     else if (C < 1 || C > ISO_PREDICT_MAX_COMPS) why = "C must be 1 to 3 components";
     else if (m->n0 < 2 || m->n1 < 2 || m->nk < 2) why = "every model axis needs at least 2 nodes";
@@ -352,30 +321,15 @@ int prepare(const char* who, const iso_predict_model_table* m, const iso_predict
     else if ((int64_t)m->n0 * m->n1 * m->nk * 4 > INT32_MAX) why = "model table too large (more than 2^31 - 1 entries)";
     else if ((double)bc->nT * bc->ng * bc->nf * bc->nA * bc->B > (double)INT32_MAX)
         why = "BC table too large (more than 2^31 - 1 entries)";
-    else if (ens_begin < 0 || n_ens_out < 1 || (int64_t)ens_begin + n_ens_out > n_ens)
-        why = "ensemble range [ens_begin, ens_begin + n_ens_out) must be non-empty and inside [0, n_ens)";
-    else if ((int64_t)n_ens * W > INT32_MAX) why = "more than 2^31 - 1 rows (split the batch)";
+    else if ((why = chain_shape_error(CHAIN_CHECK_RANGE | CHAIN_CHECK_ROWS, s))) {}
     else if (nsteps * W > INT32_MAX) why = "more than 2^31 - 1 samples an ensemble";
     else if (ndim > 256) why = "more than 256 parameters";
     else if (i_dist < 0 || i_dist >= ndim) why = "i_dist is outside [0, ndim)";
     else if (i_AV < 0 || i_AV >= ndim) why = "i_AV is outside [0, ndim)";
-    if (!why)
-        for (int c = 0; c < C * 3; ++c)
-            if (comps[c] < 0 || comps[c] >= ndim) why = "a component's parameter index is outside [0, ndim)";
-    if (why) {
-        snprintf(buf, sizeof buf, "%s: %s", who, why);
-        return fail(ISO_PREDICT_ERR_INVALID, buf);
-    }
+    else why = chain_shape_error(CHAIN_CHECK_COMPS, s);
+    if (why) return fail(ISO_PREDICT_ERR_INVALID, who, why);
     const int64_t rows = (int64_t)n_ens * W;
-    if (layout == ISO_PREDICT_PARAM_MAJOR) {
-        A.st_t = (int64_t)ndim * rows;
-        A.st_d = rows;
-        A.st_w = 1;
-    } else {
-        A.st_t = rows * ndim;
-        A.st_d = 1;
-        A.st_w = ndim;
-    }
+    A.st = chain_strides(layout, rows, ndim);
     A.chain = chain;
     A.lnprob = lnprob;
     A.obs_val = obs_val;
@@ -395,7 +349,7 @@ int prepare(const char* who, const iso_predict_model_table* m, const iso_predict
     A.n_ens_out = n_ens_out;
     A.n = (int32_t)(nsteps * W);
     for (int c = 0; c < MAXC; ++c)
-        A.comp[c] = c < C ? (comps[3 * c] | comps[3 * c + 1] << 8 | comps[3 * c + 2] << 16) : 0;
+        A.comp[c] = c < C ? pack_comp(comps[3 * c], comps[3 * c + 1], comps[3 * c + 2]) : 0;
     return 0;
 }
 
@@ -489,8 +443,8 @@ int iso_predict_chain_host(const iso_predict_model_table* model, const iso_predi
             if (out->map_index) out->map_index[e] = bi;
             if (out->map_pars) {
                 const int t = bi < 0 ? 0 : (int)(bi / W), w = bi < 0 ? 0 : (int)(bi - (int64_t)t * W);
-                const double* row = chain + (int64_t)t * A.st_t + ((int64_t)(ens_begin + e) * W + w) * A.st_w;
-                for (int d = 0; d < ndim; ++d) out->map_pars[(int64_t)e * ndim + d] = bi < 0 ? qnan() : row[d * A.st_d];
+                const double* row = chain + (int64_t)t * A.st.st_t + ((int64_t)(ens_begin + e) * W + w) * A.st.st_w;
+                for (int d = 0; d < ndim; ++d) out->map_pars[(int64_t)e * ndim + d] = bi < 0 ? qnan() : row[d * A.st.st_d];
             }
         }
     }

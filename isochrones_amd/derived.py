@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _cabi, _derived_cabi, device as dev
+from . import _cabi, _chain, _derived_cabi, device as dev
 
 #: what ``derived=True`` asks for in a catalog fit, as far as the model grid has the column and the fit does not sample it
 DEFAULT_PROPS = ("mass", "radius", "age", "Teff", "logg")
@@ -93,19 +93,11 @@ class DerivedTable:
 
 def derived_tables(ic, columns, device):
     """The packed tables of ``columns`` (one per 8 columns), made once per (interpolator, device, column tuple) and remade
-    when the model table was rebuilt (the rule of ``_solve_table``: compare the table's generation); ``ic.release()`` drops
-    them."""
-    dfi = ic.model_grid.interp
-    gen = dfi._handles.generation
-    cache = ic.__dict__.setdefault("_derived_tables", {})
-    key = (device, tuple(columns))
-    entry = cache.get(key)
-    if entry is None or entry[0] != gen:
-        icols = [dfi.column_index[c] for c in columns]
-        M = _derived_cabi.MAX_COLS
-        entry = cache[key] = (gen, [DerivedTable(dfi.grid, icols[i:i + M], dfi.index_columns, device)
-                                    for i in range(0, len(icols), M)])
-    return entry[1]
+    when the model table was rebuilt (``_chain.cached_by_generation``); ``ic.release()`` drops them."""
+    dfi, M = ic.model_grid.interp, _derived_cabi.MAX_COLS
+    icols = [dfi.column_index[c] for c in columns]
+    return _chain.cached_by_generation(ic, "_derived_tables", (device, tuple(columns)), dfi._handles.generation, lambda: [
+        DerivedTable(dfi.grid, icols[i:i + M], dfi.index_columns, device) for i in range(0, len(icols), M)])
 
 
 def derive_storage(storage, n_ens, nwalkers, ic, props, N=1, layout=_cabi.CHAIN_PARAM_MAJOR, ens_begin=0, n_ens_out=None):
@@ -118,18 +110,10 @@ def derive_storage(storage, n_ens, nwalkers, ic, props, N=1, layout=_cabi.CHAIN_
     labels, cols = resolve_props(ic, props, N)
     comps = components(ic, N)
     n_ens, W = int(n_ens), int(nwalkers)
-    if not (dev.is_tensor(storage) and storage.is_cuda and storage.dtype == torch.float64):
-        raise ValueError("derived properties take a float64 CUDA tensor")
-    rows_axis = 2 if layout == _cabi.CHAIN_PARAM_MAJOR else 1
-    if storage.dim() != 3 or storage.shape[rows_axis] != n_ens * W:
-        raise ValueError("chain storage is [nsteps, ndim, n_ens * nwalkers] (parameter-major) or [nsteps, n_ens * nwalkers, ndim]")
-    nsteps, ndim = int(storage.shape[0]), int(storage.shape[3 - rows_axis])
-    if nsteps < 1:
-        raise ValueError("no stored chain")
+    x, nsteps, ndim = _chain.check_storage(storage, n_ens, W, layout, "derived properties take")
     if ndim < len(fit_param_names(ic, N)):
         raise ValueError("the chain has %d parameters, a fit on this grid samples %d" % (ndim, len(fit_param_names(ic, N))))
-    n_out = n_ens - int(ens_begin) if n_ens_out is None else int(n_ens_out)
-    x = storage.contiguous()
+    n_out = n_ens - int(ens_begin) if n_ens_out is None else int(n_ens_out)     # (the range is the C call's to check)
     device = x.device.index
     Cn, Qt, R = len(comps), len(cols), n_out * W
     out = torch.empty(nsteps, Cn * Qt, max(R, 0), dtype=torch.float64, device=x.device)
@@ -161,22 +145,9 @@ def chain_derived(chain, ic, props, N=1, n_ens=None, nwalkers=None):
     (``{label}_{k}`` for N > 1).  ``props`` items are a column name or a ``(label, column)`` pair.  NaN where the sample lies
     off the grid or next to its NaN padding."""
     import torch
-    if (n_ens is None) != (nwalkers is None):
-        raise ValueError("give both n_ens and nwalkers (parameter-major storage) or neither (a [S, W, T, D] chain)")
     if not dev.is_tensor(chain) or chain.dtype != torch.float64 or not chain.is_cuda:
         raise ValueError("chain_derived takes a float64 CUDA tensor")
-    single = False
-    if nwalkers is not None:
-        storage = chain
-    else:
-        if chain.dim() == 3:
-            chain, single = chain[None], True
-        if chain.dim() != 4:
-            raise ValueError("chain must be [S, W, T, D] or [W, T, D]")
-        n_ens, nwalkers = int(chain.shape[0]), int(chain.shape[1])
-        t = chain.permute(2, 3, 0, 1)                                           # [T, D, S, W]
-        storage = t.contiguous().reshape(t.shape[0], t.shape[1], n_ens * nwalkers)
+    storage, n_ens, nwalkers, single = _chain.as_storage(chain, n_ens, nwalkers)
     labels, _ = resolve_props(ic, props, N)
     out, _ = derive_storage(storage, n_ens, nwalkers, ic, props, N)
-    view = out.view(out.shape[0], out.shape[1], int(n_ens), int(nwalkers)).permute(2, 3, 0, 1)
-    return (view[0] if single else view), expand_labels(labels, N)
+    return _chain.from_storage(out, n_ens, nwalkers, single), expand_labels(labels, N)

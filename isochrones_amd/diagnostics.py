@@ -10,7 +10,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import _cabi, _diag_cabi
+from . import _cabi, _chain, _diag_cabi
 
 ChainDiagnostics = namedtuple("ChainDiagnostics", ["tau", "window", "window_ok", "ess", "rhat"])
 ChainDiagnostics.__doc__ = """Per-pair diagnostics, each [S, D] (or [D] for a single ensemble): ``tau`` integrated
@@ -34,23 +34,16 @@ def diag_storage(storage, n_ens, nwalkers, c=_diag_cabi.DEFAULT_C, max_lag=_diag
     import ctypes as C
     c, max_lag = _check(c, max_lag)
     n_ens, nwalkers = int(n_ens), int(nwalkers)
-    if len(storage.shape) != 3 or storage.shape[2] != n_ens * nwalkers:
-        raise ValueError("parameter-major storage is [nsteps, ndim, n_ens * nwalkers]")
-    nsteps, ndim = int(storage.shape[0]), int(storage.shape[1])
-    if nsteps < 1:
-        raise ValueError("no stored chain")
+    x, nsteps, ndim = _chain.check_storage(storage, n_ens, nwalkers, _cabi.CHAIN_PARAM_MAJOR, "chain_diagnostics takes",
+                                           host=True)
     lib = _diag_cabi.lib()
-    if isinstance(storage, np.ndarray):
-        x = np.ascontiguousarray(storage, dtype=np.float64)
+    if isinstance(x, np.ndarray):
         out = np.empty((n_ens, ndim, _diag_cabi.NOUT))
         _diag_cabi.check(lib.iso_diag_chain_host(x.ctypes.data_as(C.c_void_p), _cabi.CHAIN_PARAM_MAJOR, nsteps, n_ens, nwalkers,
                                                  ndim, c, max_lag, out.ctypes.data_as(C.c_void_p), None))
         return out
     import torch
     from . import device as dev
-    if not (storage.is_cuda and storage.dtype == torch.float64):
-        raise ValueError("chain_diagnostics takes a float64 CUDA tensor or a host numpy array")
-    x = storage.contiguous()
     out = torch.empty(n_ens, ndim, _diag_cabi.NOUT, dtype=torch.float64, device=x.device)
     with torch.cuda.device(x.device):
         _diag_cabi.check(lib.iso_diag_chain(dev.ptr(x), _cabi.CHAIN_PARAM_MAJOR, nsteps, n_ens, nwalkers, ndim, c, max_lag,
@@ -64,20 +57,7 @@ def chain_diagnostics(chain, c=_diag_cabi.DEFAULT_C, max_lag=_diag_cabi.DEFAULT_
     the parameter-major storage ``[T, D, n_ens * nwalkers]`` itself.  ``c`` is Sokal's window factor, ``max_lag`` the largest
     lag summed.  Returns a :class:`ChainDiagnostics` of ``[S, D]`` (``[D]`` for a ``[W, T, D]`` chain) arrays of the
     input's kind."""
-    host = isinstance(chain, np.ndarray)
-    if (n_ens is None) != (nwalkers is None):
-        raise ValueError("give both n_ens and nwalkers (parameter-major storage) or neither (a [S, W, T, D] chain)")
-    single = False
-    if nwalkers is not None:
-        storage = chain
-    else:
-        if len(chain.shape) == 3:
-            chain, single = chain[None], True
-        if len(chain.shape) != 4:
-            raise ValueError("chain must be [S, W, T, D] or [W, T, D]")
-        n_ens, nwalkers = int(chain.shape[0]), int(chain.shape[1])
-        t = chain.transpose(2, 3, 0, 1) if host else chain.permute(2, 3, 0, 1)            # [T, D, S, W]
-        storage = (np.ascontiguousarray(t) if host else t.contiguous()).reshape(t.shape[0], t.shape[1], n_ens * nwalkers)
+    storage, n_ens, nwalkers, single = _chain.as_storage(chain, n_ens, nwalkers)
     out = diag_storage(storage, n_ens, nwalkers, c, max_lag)
     if single:
         out = out[0]

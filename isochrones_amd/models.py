@@ -454,15 +454,12 @@ class ModelGridInterpolator:
 
     def _solve_table(self, device):
         """Device copies of the column, the axes and the ranges: made once per device, remade when the table was
-        rebuilt (the rule of ``_eep_handles``: compare the table's generation)."""
-        from . import solve
+        rebuilt (``_chain.cached_by_generation``, as the tables of the derived properties and the predictive check)."""
+        from . import _chain, solve
         col, ranges = self._solve_host()
-        gen = self.model_grid.interp._handles.generation
-        tables = self.__dict__.setdefault("_solve_tables", {})
-        entry = tables.get(device)
-        if entry is None or entry[0] != gen:
-            entry = tables[device] = (gen, solve.DeviceTable(col, self.model_grid.interp.index_columns, ranges, device))
-        return entry[1]
+        dfi = self.model_grid.interp
+        return _chain.cached_by_generation(self, "_solve_tables", device, dfi._handles.generation,
+                                           lambda: solve.DeviceTable(col, dfi.index_columns, ranges, device))
 
     def solve_eep(self, mass, age, feh):
         """The EEP at which a star of given (mass, log10 age, feh) sits, exact to rounding: the interpolated ``age``

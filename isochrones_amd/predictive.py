@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _cabi, _predict_cabi, derived as dv, device as dev
+from . import _cabi, _chain, _predict_cabi, derived as dv, device as dev
 
 #: the terms after the bands, in the kernel's order
 SPEC_TERMS = ("Teff", "logg", "feh", "parallax")
@@ -112,15 +112,11 @@ class PredictTables:
 
 
 def predict_tables(ic, bands, device):
-    """The packed tables, made once per (interpolator, device, bands) and remade when the model table was rebuilt (the rule
-    of ``derived_tables``: compare the table's generation); ``ic.release()`` drops them."""
+    """The packed tables, made once per (interpolator, device, bands) and remade when the model or the BC table was rebuilt
+    (``_chain.cached_by_generation``); ``ic.release()`` drops them."""
     gen = (ic.model_grid.interp._handles.generation, ic.bc_grid.interp._handles.generation)
-    cache = ic.__dict__.setdefault("_predict_tables", {})
-    key = (device, tuple(bands))
-    entry = cache.get(key)
-    if entry is None or entry[0] != gen:
-        entry = cache[key] = (gen, PredictTables(ic, bands, device))
-    return entry[1]
+    return _chain.cached_by_generation(ic, "_predict_tables", (device, tuple(bands)), gen,
+                                       lambda: PredictTables(ic, bands, device))
 
 
 def _check_bands(ic, bands):
@@ -145,14 +141,7 @@ def predict_storage(storage, lnprob, n_ens, nwalkers, ic, bands, obs, N=1, layou
     bands = _check_bands(ic, bands)
     comps = dv.components(ic, N)
     n_ens, W = int(n_ens), int(nwalkers)
-    if not (dev.is_tensor(storage) and storage.is_cuda and storage.dtype == torch.float64):
-        raise ValueError("the posterior-predictive check takes a float64 CUDA tensor")
-    rows_axis = 2 if layout == _cabi.CHAIN_PARAM_MAJOR else 1
-    if storage.dim() != 3 or storage.shape[rows_axis] != n_ens * W:
-        raise ValueError("chain storage is [nsteps, ndim, n_ens * nwalkers] (parameter-major) or [nsteps, n_ens * nwalkers, ndim]")
-    nsteps, ndim = int(storage.shape[0]), int(storage.shape[3 - rows_axis])
-    if nsteps < 1:
-        raise ValueError("no stored chain")
+    x, nsteps, ndim = _chain.check_storage(storage, n_ens, W, layout, "the posterior-predictive check takes")
     if ndim < len(dv.fit_param_names(ic, N)):
         raise ValueError("the chain has %d parameters, a fit on this grid samples %d" % (ndim, len(dv.fit_param_names(ic, N))))
     if lnprob is not None:
@@ -164,7 +153,6 @@ def predict_storage(storage, lnprob, n_ens, nwalkers, ic, bands, obs, N=1, layou
     if int(ens_begin) < 0 or n_out < 1 or int(ens_begin) + n_out > n_ens:
         raise ValueError("ensemble range [ens_begin, ens_begin + n_ens_out) must be non-empty and inside [0, n_ens)")
     packed = pack_obs(obs, bands, n_ens)
-    x = storage.contiguous()
     lp = None if lnprob is None else lnprob.contiguous()
     device = x.device.index
     B, R = len(bands), n_out * W
@@ -199,24 +187,17 @@ def chain_predictive(chain, lnprob, ic, bands, obs, N=1):
     import torch
     if not dev.is_tensor(chain) or chain.dtype != torch.float64 or not chain.is_cuda:
         raise ValueError("chain_predictive takes a float64 CUDA tensor")
-    single = chain.dim() == 3
-    if single:
-        chain = chain[None]
-        lnprob = None if lnprob is None else lnprob[None]
-    if chain.dim() != 4:
-        raise ValueError("chain must be [S, W, T, D] or [W, T, D]")
-    S, W = int(chain.shape[0]), int(chain.shape[1])
-    t = chain.permute(2, 3, 0, 1)                                               # [T, D, S, W]
-    storage = t.contiguous().reshape(t.shape[0], t.shape[1], S * W)
-    lp = None
+    storage, S, W, single = _chain.as_storage(chain)
+    nsteps, lp = int(storage.shape[0]), None
     if lnprob is not None:
-        if not dev.is_tensor(lnprob) or tuple(lnprob.shape) != (S, W, int(chain.shape[2])):
+        lnprob = lnprob[None] if single else lnprob
+        if not dev.is_tensor(lnprob) or tuple(lnprob.shape) != (S, W, nsteps):
             raise ValueError("lnprob must be [S, W, T] (or [W, T])")
-        lp = lnprob.permute(2, 0, 1).contiguous().reshape(int(chain.shape[2]), S * W)
+        lp = lnprob.permute(2, 0, 1).contiguous().reshape(nsteps, S * W)
     r = predict_storage(storage, lp, S, W, ic, bands, obs, N=N)
-    r.mags = r.mags.view(r.mags.shape[0], r.mags.shape[1], S, W).permute(2, 3, 0, 1)
+    r.mags = _chain.from_storage(r.mags, S, W, single)
     if single:
-        r.mags, r.term_chi2, r.ppc, r.n_bad, r.mag_nan = r.mags[0], r.term_chi2[0], r.ppc[0], r.n_bad[0], r.mag_nan[0]
+        r.term_chi2, r.ppc, r.n_bad, r.mag_nan = r.term_chi2[0], r.ppc[0], r.n_bad[0], r.mag_nan[0]
         if r.map_index is not None:
             r.map_index, r.map_pars = r.map_index[0], r.map_pars[0]
     return r

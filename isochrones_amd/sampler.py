@@ -270,21 +270,16 @@ class FusedEnsembleSampler:
         (``iso_chain_quantiles``: one wavefront per (ensemble, parameter) pair up to 6 656 values, a workgroup up to
         8 192, refinement passes streamed from the chain beyond - the reference's default 300 walkers x 100
         iterations); only more than 8 quantile levels at once fall back to a framework sort."""
-        import ctypes as C
         import torch
-        from . import _cabi, device as dev
+        from . import _chain
         if self._chain is None:
             raise ValueError("no stored chain")
         nsteps = self._chain.shape[0]
         q = np.ascontiguousarray(q, dtype=np.float64)
         if q.size <= 8:
             out = torch.empty(self.n_ensembles, self.ndim, q.size, dtype=torch.float64, device=self.device)
-            chain = self._chain.contiguous()
-            _cabi.check(_cabi.lib().iso_chain_quantiles_layout(dev.context(self.device_index), dev.ptr(chain),
-                                                               _cabi.CHAIN_PARAM_MAJOR, nsteps, self.n_ensembles,
-                                                               self.nwalkers, self.ndim,
-                                                               q.ctypes.data_as(C.POINTER(C.c_double)), q.size,
-                                                               dev.ptr(out), dev.stream_ptr(self.device_index)))
+            _chain.quantiles_layout(self.device_index, self._chain.contiguous(), nsteps, self.n_ensembles, self.nwalkers,
+                                    self.ndim, q, out)
         else:
             flat = self._chain.view(nsteps, self.ndim, self.n_ensembles, self.nwalkers).permute(2, 1, 0, 3)
             srt = torch.sort(flat.reshape(self.n_ensembles, self.ndim, -1), dim=2).values
@@ -311,13 +306,10 @@ class FusedEnsembleSampler:
         :class:`isochrones_amd.diagnostics.ChainDiagnostics` of [S, ndim] (model: [ndim]) CUDA tensors - ``tau`` (integrated
         autocorrelation time, Sokal's window ``c``), ``window``, ``window_ok``, ``ess`` and split ``rhat``.  One launch of
         ``iso_diag_chain`` on the parameter-major storage, no copy; a model sampler and a catalog sampler alike."""
-        from . import _diag_cabi, diagnostics as dg
+        from . import diagnostics as dg
         if self._chain is None:
             raise ValueError("no stored chain")
-        out = dg.diag_storage(self._chain, self.n_ensembles, self.nwalkers, c, max_lag)
-        if not self._stacked:
-            out = out[0]
-        return dg.ChainDiagnostics(*(out[..., i] for i in range(_diag_cabi.NOUT)))
+        return dg.chain_diagnostics(self.chain, c, max_lag)       # (a view of the storage: passed on as it is)
 
     def get_autocorr_time(self, c=5.0, max_lag=1024):
         """Integrated autocorrelation time per parameter in steps (named as emcee names it), [S, ndim] or [ndim]."""
@@ -339,8 +331,7 @@ class FusedEnsembleSampler:
         from . import derived as dv
         if self._chain is None:
             raise ValueError("no stored chain")
-        out, names = dv.chain_derived(self._chain, ic, props, N=N, n_ens=self.n_ensembles, nwalkers=self.nwalkers)
-        return (out if self._stacked else out[0]), names
+        return dv.chain_derived(self.chain, ic, props, N=N)       # (a view of the storage: passed on as it is)
 
     def derived_quantiles(self, ic, props, q=(0.5, 0.16, 0.84), N=1, budget_bytes=None):
         """Per-ensemble quantiles of the derived chain and its NaN counts: ``(quantiles, nan_count)``, [S, C*Q, len(q)]
@@ -348,35 +339,19 @@ class FusedEnsembleSampler:
         whole ensembles of at most ``budget_bytes`` (default ``derived.DERIVED_BUDGET_BYTES``), each slice by one
         ``iso_derived_chain`` launch per 8 columns and summarised by one ``iso_chain_quantiles_layout`` call where it lies.
         A column of an ensemble with a NaN sample (off the grid, or next to its NaN padding) has NaN quantiles."""
-        import ctypes as C
-        import torch
-        from . import _cabi, derived as dv, device as dev
+        from . import _chain, derived as dv
         if self._chain is None:
             raise ValueError("no stored chain")
-        q = np.ascontiguousarray(q, dtype=np.float64)
-        if q.size < 1 or q.size > 8:
-            raise ValueError("derived_quantiles takes 1 to 8 quantile levels per call (the quantile kernel's limit)")
         budget = dv.DERIVED_BUDGET_BYTES if budget_bytes is None else int(budget_bytes)
         labels, _ = dv.resolve_props(ic, props, N)
         CQ = len(dv.components(ic, N)) * len(labels)
         nsteps, S, W = int(self._chain.shape[0]), self.n_ensembles, self.nwalkers
-        per_ens = nsteps * CQ * W * 8
-        step = budget // per_ens
-        if step < 1:
-            raise ValueError("the derived chain of one ensemble takes %d bytes, more than budget_bytes = %d: raise the "
-                             "budget, ask for fewer columns or thin the chain" % (per_ens, budget))
         chain = self._chain.contiguous()
-        out = torch.empty(S, CQ, q.size, dtype=torch.float64, device=self.device)
-        counts = torch.empty(S, CQ, dtype=torch.int32, device=self.device)
-        for s0 in range(0, S, step):
-            n = min(step, S - s0)
-            d, nc = dv.derive_storage(chain, S, W, ic, props, N=N, ens_begin=s0, n_ens_out=n)
-            _cabi.check(_cabi.lib().iso_chain_quantiles_layout(dev.context(self.device_index), dev.ptr(d),
-                                                               _cabi.CHAIN_PARAM_MAJOR, nsteps, n, W, CQ,
-                                                               q.ctypes.data_as(C.POINTER(C.c_double)), q.size,
-                                                               dev.ptr(out[s0:s0 + n]), dev.stream_ptr(self.device_index)))
-            counts[s0:s0 + n] = nc
-        out = torch.where((counts > 0)[:, :, None], torch.full_like(out, float("nan")), out)
+        out, counts = _chain.sliced_quantiles(
+            self.device_index, nsteps, S, W, CQ, q, budget,
+            lambda s0, n: dv.derive_storage(chain, S, W, ic, props, N=N, ens_begin=s0, n_ens_out=n), "derived_quantiles",
+            "the derived chain of one ensemble takes %d bytes, more than budget_bytes = %d: raise the budget, ask for fewer "
+            "columns or thin the chain")
         return (out, counts) if self._stacked else (out[0], counts[0])
 
     def predictive(self, ic, obs, bands=None, q=(0.5, 0.16, 0.84), N=1, budget_bytes=None):
@@ -387,45 +362,31 @@ class FusedEnsembleSampler:
         slices of whole ensembles of at most ``budget_bytes`` (default ``predictive.PREDICT_BUDGET_BYTES``), each slice by one
         ``iso_predict_chain`` launch on the parameter-major storage and summarised by one ``iso_chain_quantiles_layout`` call
         where it lies.  A band of an ensemble with a NaN sample (off either grid) has NaN quantiles."""
-        import ctypes as C
         import torch
-        from . import _cabi, predictive as pv, device as dev
+        from . import _chain, predictive as pv
         if self._chain is None:
             raise ValueError("no stored chain")
-        q = np.ascontiguousarray(q, dtype=np.float64)
-        if q.size < 1 or q.size > 8:
-            raise ValueError("predictive takes 1 to 8 quantile levels per call (the quantile kernel's limit)")
         budget = pv.PREDICT_BUDGET_BYTES if budget_bytes is None else int(budget_bytes)
         bands = pv._check_bands(ic, bands)
         B = len(bands)
         nsteps, S, W = int(self._chain.shape[0]), self.n_ensembles, self.nwalkers
-        per_ens = nsteps * B * W * 8
-        step = budget // per_ens
-        if step < 1:
-            raise ValueError("the magnitude chain of one ensemble takes %d bytes, more than budget_bytes = %d: raise the "
-                             "budget, ask for fewer bands or thin the chain" % (per_ens, budget))
         packed = pv.pack_obs(obs, bands, S)
         dobs = packed if isinstance(packed, pv.DeviceObs) else pv.DeviceObs(packed[0], packed[1], self.device_index)
         chain, lnp = self._chain.contiguous(), self._lnprob.contiguous()
         f64 = dict(dtype=torch.float64, device=self.device)
         out = dict(ppc=torch.empty(S, **f64), term_chi2=torch.empty(S, B + 4, **f64),
-                   n_bad=torch.empty(S, dtype=torch.int32, device=self.device),
-                   mag_quantiles=torch.empty(S, B, q.size, **f64), map_pars=torch.empty(S, self.ndim, **f64),
-                   map_index=torch.empty(S, dtype=torch.int64, device=self.device))
-        mag_nan = torch.empty(S, B, dtype=torch.int32, device=self.device)
-        for s0 in range(0, S, step):
-            n = min(step, S - s0)
+                   n_bad=torch.empty(S, dtype=torch.int32, device=self.device), mag_quantiles=None,
+                   map_pars=torch.empty(S, self.ndim, **f64), map_index=torch.empty(S, dtype=torch.int64, device=self.device))
+
+        def make(s0, n):
             r = pv.predict_storage(chain, lnp, S, W, ic, bands, dobs, N=N, ens_begin=s0, n_ens_out=n)
-            _cabi.check(_cabi.lib().iso_chain_quantiles_layout(dev.context(self.device_index), dev.ptr(r.mags),
-                                                               _cabi.CHAIN_PARAM_MAJOR, nsteps, n, W, B,
-                                                               q.ctypes.data_as(C.POINTER(C.c_double)), q.size,
-                                                               dev.ptr(out["mag_quantiles"][s0:s0 + n]),
-                                                               dev.stream_ptr(self.device_index)))
-            mag_nan[s0:s0 + n] = r.mag_nan
-            out["ppc"][s0:s0 + n], out["term_chi2"][s0:s0 + n], out["n_bad"][s0:s0 + n] = r.ppc, r.term_chi2, r.n_bad
-            out["map_pars"][s0:s0 + n], out["map_index"][s0:s0 + n] = r.map_pars, r.map_index
-        out["mag_quantiles"] = torch.where((mag_nan > 0)[:, :, None], torch.full_like(out["mag_quantiles"], float("nan")),
-                                           out["mag_quantiles"])
+            for k in ("ppc", "term_chi2", "n_bad", "map_pars", "map_index"):
+                out[k][s0:s0 + n] = getattr(r, k)
+            return r.mags, r.mag_nan
+        out["mag_quantiles"], _ = _chain.sliced_quantiles(
+            self.device_index, nsteps, S, W, B, q, budget, make, "predictive",
+            "the magnitude chain of one ensemble takes %d bytes, more than budget_bytes = %d: raise the budget, ask for fewer "
+            "bands or thin the chain")
         if not self._stacked:
             out = {k: v[0] for k, v in out.items()}
         out["bands"] = bands
