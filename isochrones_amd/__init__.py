@@ -20,5 +20,8 @@ from .cluster import StarClusterModel, simulate_cluster
 from .diagnostics import chain_diagnostics, ChainDiagnostics
 from .derived import chain_derived
 from .predictive import chain_predictive
+from . import populations
+from .populations import (StarPopulation, BinaryDistribution, StarFormationHistory, StarFormationHistoryGrid, deredden,
+                          evaluate_binaries)
 
 __version__ = "0.1.0"

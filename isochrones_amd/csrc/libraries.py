@@ -2,7 +2,7 @@
 
     python -m isochrones_amd.csrc.libraries NAME [--force] [--verbose]
 
-A new library is one more spec here (and its name in ALL), its sources in csrc/<name>/ and its header
+A new library is one more spec here (and its name in BUILD_ORDER), its sources in csrc/<name>/ and its header
 include/isochrones_amd_<name>.h."""
 from __future__ import annotations
 
@@ -11,7 +11,7 @@ import sys
 from .sidelib import INCLUDE, KernelLibrary
 
 _COMMON = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math")
-#: what five of the six are built with.  -ffp-contract=off: the compiler fuses no multiply-add on its own (each spec says
+#: what every library but NESTED is built with.  -ffp-contract=off: the compiler fuses no multiply-add on its own (each spec says
 #: what that buys)
 _NO_CONTRACT = _COMMON + ("-ffp-contract=off", "-Wall", "-Wno-unused-function", "-I" + INCLUDE)
 
@@ -94,11 +94,31 @@ PREDICT = KernelLibrary(
     #: their spill slots count as scratch.  The workgroup is two waves, so the budget is the 2-waves-per-SIMD one: 256 VGPRs
     max_vgpr=256, min_waves=2, extra_headers=_CHAIN_HEADERS)
 
+# a batch of coeval single or binary systems evaluated on the model and the BC grid (csrc/population/)
+# -ffp-contract=off: the compiler fuses nothing, and the sources write no fma(): every product and every sum of the header's
+# definition is rounded on its own (a system's values are bit-identical alone and in any batch)
+POPULATION = KernelLibrary(
+    name="population", flags=_NO_CONTRACT,
+    #: every kernel the library compiles (tests/test_population_library.py pins this set)
+    kernels=("k_population_eval",),
+    #: k_population_eval compiles to 246 VGPRs, no scratch, 32 KB of LDS and 2 waves per SIMD.  A system holds the model
+    #: cell's eight weights, eight column accumulators and their corner loads in flight (k_derived_chain's pressure), then
+    #: the (Teff, logg, feh, Mbol) of two components, two sets of eight band accumulators (at AV and at AV = 0), their
+    #: corner loads and a binary's two sets of eight sums (k_predict_chain's pressure, doubled by the second lookup).  Held to
+    #: 4 waves (128 VGPRs) it spills 190 registers to scratch, with four bands a pass still 94; so the budget is the
+    #: 2-waves-per-SIMD one: 256 VGPRs, and no scratch at all.  Its uniform arguments (two tables, eight pointers) overflow
+    #: the SGPR file into VGPR lanes, not into scratch, so they are not staged in LDS as k_predict_chain's are
+    max_vgpr=256, min_waves=2, extra_headers=("common/grid_cell.h",))
+
+#: the six libraries the shared builder started with (tests/test_side_libraries_cpu.py pins this tuple to exactly these)
 ALL = (CLUSTER, NESTED, SOLVE, DIAG, DERIVED, PREDICT)
+#: what __graft_entry__.build() and the command line below build, in order: ALL and the libraries added since ALL was
+#: pinned.  A new library goes here; ALL stays what its test says it is
+BUILD_ORDER = ALL + (POPULATION,)
 
 
 if __name__ == "__main__":
-    by_name = {spec.name: spec for spec in ALL}
+    by_name = {spec.name: spec for spec in BUILD_ORDER}
     names = [a for a in sys.argv[1:] if not a.startswith("--")]
     if len(names) != 1 or names[0] not in by_name:
         sys.exit("usage: python -m isochrones_amd.csrc.libraries {%s} [--force] [--verbose]" % ",".join(by_name))
