@@ -23,5 +23,7 @@ from .predictive import chain_predictive
 from . import populations
 from .populations import (StarPopulation, BinaryDistribution, StarFormationHistory, StarFormationHistoryGrid, deredden,
                           evaluate_binaries)
+from . import hierarchical
+from .hierarchical import PopulationModel, PopulationPosterior, PowerLaw, TruncatedGaussian, Fixed
 
 __version__ = "0.1.0"

@@ -1,8 +1,9 @@
-"""The side libraries, each a spec for sidelib.KernelLibrary, in the order __graft_entry__.build() builds them.
+"""The side libraries, each a spec for sidelib.KernelLibrary, in the order __graft_entry__.build() builds them
+(BUILD_ORDER + ADDED).
 
     python -m isochrones_amd.csrc.libraries NAME [--force] [--verbose]
 
-A new library is one more spec here (and its name in BUILD_ORDER), its sources in csrc/<name>/ and its header
+A new library is one more spec here (and its name in ADDED), its sources in csrc/<name>/ and its header
 include/isochrones_amd_<name>.h."""
 from __future__ import annotations
 
@@ -110,15 +111,32 @@ POPULATION = KernelLibrary(
     #: the SGPR file into VGPR lanes, not into scratch, so they are not staged in LDS as k_predict_chain's are
     max_vgpr=256, min_waves=2, extra_headers=("common/grid_cell.h",))
 
+# the hierarchical (population) likelihood from the stored chains of a catalog (csrc/hier/)
+# -ffp-contract=off: the compiler fuses nothing, and the sources write no fma(): every product and every sum of the header's
+# definition is rounded on its own (a star's row is bit-identical alone, in any batch and in any tiling of the hyper rows)
+HIER = KernelLibrary(
+    name="hier", flags=_NO_CONTRACT,
+    #: every kernel the library compiles (tests/test_hier_library.py pins this set)
+    kernels=("k_hier_stars", "k_hier_total"),
+    #: k_hier_stars compiles to 153 VGPRs, no scratch, 3.3 KB of LDS and 3 waves per SIMD.  A lane holds the maximum, sum w and
+    #: sum w^2 of the tile's eight rows (48 registers), the sample's eight log ratios (16) and the temporaries of eight
+    #: inlined family evaluations, the FEH one with three exp and a log in flight.  Held to 4 waves (128 VGPRs) it spills 45
+    #: registers to scratch; the per-(row, sample) exp binds, not latency, so the budget is the 3-waves-per-SIMD one: 168
+    #: VGPRs, and no scratch at all.  k_hier_total is 17 VGPRs at 8 waves
+    max_vgpr=168, min_waves=3, extra_headers=_CHAIN_HEADERS)
+
 #: the six libraries the shared builder started with (tests/test_side_libraries_cpu.py pins this tuple to exactly these)
 ALL = (CLUSTER, NESTED, SOLVE, DIAG, DERIVED, PREDICT)
 #: what __graft_entry__.build() and the command line below build, in order: ALL and the libraries added since ALL was
 #: pinned.  A new library goes here; ALL stays what its test says it is
 BUILD_ORDER = ALL + (POPULATION,)
+#: the libraries added after BUILD_ORDER was pinned in its turn (tests/test_population_library.py); __graft_entry__.build()
+#: and the command line below go through BUILD_ORDER + ADDED.  The next library goes here
+ADDED = (HIER,)
 
 
 if __name__ == "__main__":
-    by_name = {spec.name: spec for spec in BUILD_ORDER}
+    by_name = {spec.name: spec for spec in BUILD_ORDER + ADDED}
     names = [a for a in sys.argv[1:] if not a.startswith("--")]
     if len(names) != 1 or names[0] not in by_name:
         sys.exit("usage: python -m isochrones_amd.csrc.libraries {%s} [--force] [--verbose]" % ",".join(by_name))

@@ -1,0 +1,435 @@
+"""The hierarchical (population) likelihood of a catalog from the chains its fit left on the device: which mass function,
+metallicity distribution and age distribution did the stars come from?  Every star's posterior samples are reweighted
+from the prior the fit used (the *interim* prior) to a population density (Hogg, Myers & Bovy 2010),
+
+    ln L(theta) = sum_s ln (1/M) sum_m  prod_q f_q(x_q[s][m]; theta) / f0_q(x_q[s][m]),
+
+by the HIP kernels of libiso_hier.so (``iso_hier_lnlike``; the definition is in include/isochrones_amd_hier.h) on the stored
+chain where it lies: no refit, no copy to the host.  A column that is a parameter of the fit is read from the sampler's
+chain; anything else (``age`` on evolution tracks, ``mass`` on isochrones) from the derived chain of
+:func:`isochrones_amd.derived.derive_storage`.  On isochrones ``mass`` is the model grid's column ``mass``: the one the
+model's EEP prior is stated in (``EEPPrior`` interpolates ``(mass, dm_deep)``).  The ratio is taken in the coordinates the
+fit's priors are stated in - the prior of the parameter EEP replaces is ``EEPPrior.orig_prior`` of that coordinate, the
+Jacobian d(orig)/d(EEP) belongs to the change of variables - so no Jacobian enters.
+
+Selection effects, densities that couple columns (mixtures across columns) and multiple systems (N > 1) are out of scope."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _cabi, _chain, _hier_cabi as hc, device as dev
+from . import priors as _p
+
+#: device memory one slice of a derived chain may take in :class:`PopulationPosterior`
+HIER_BUDGET_BYTES = 2 << 30
+
+_LOG_ROOT_2PI = math.log(math.sqrt(2 * math.pi))
+_ROOT2 = math.sqrt(2.0)
+
+
+def _erfc(x):
+    from scipy.special import erfc
+    return erfc(x)
+
+
+def records(n):
+    """``n`` zeroed ``iso_hier_record`` as a numpy structured array."""
+    return np.zeros(n, dtype=hc.RECORD)
+
+
+def prior_record(prior):
+    """The ``iso_hier_record`` (a numpy structured scalar array of shape [1]) of a device prior: ``ln f`` of the record is
+    ``prior.lnpdf``."""
+    if _p.is_host_prior(prior):
+        raise ValueError("prior %r is evaluated on the host: the hierarchical kernel needs one of "
+                         "isochrones_amd.priors.DEVICE_PRIOR_TYPES" % (prior,))
+    r = records(1)
+    lo, hi = (float(b) for b in prior.bounds)
+    r["lo"], r["hi"] = lo, hi
+    with np.errstate(all="ignore"):
+        if isinstance(prior, _p.FlatPrior):
+            r["kind"], r["p"][0, 0] = hc.FLAT, np.log(1.0 / (hi - lo))
+        elif isinstance(prior, _p.FlatLogPrior):
+            r["kind"], r["p"][0, 0] = hc.FLATLOG, np.log(_p._LN10 / (10 ** hi - 10 ** lo))
+        elif isinstance(prior, _p.PowerLawPrior):
+            r["kind"] = hc.POWERLAW
+            r["p"][0, :2] = np.log(prior._C()), prior.alpha
+        elif isinstance(prior, _p.GaussianPrior):
+            r["kind"] = hc.GAUSS
+            if not prior.bounded:
+                r["lo"], r["hi"] = -np.inf, np.inf
+            r["p"][0, :4] = (prior.mean, prior.sigma, -_LOG_ROOT_2PI - math.log(prior.sigma) - prior.lognorm,
+                             1.0 / prior.sigma)
+        elif isinstance(prior, _p.LogNormalPrior):
+            r["kind"] = hc.LOGNORMAL
+            r["p"][0, :4] = (prior.mu, prior.sigma, -_LOG_ROOT_2PI - math.log(prior.sigma) - prior.mu, 1.0 / prior.sigma)
+        elif isinstance(prior, _p.ChabrierPrior):
+            low, high = prior.low, prior.high
+            r["kind"] = hc.CHABRIER
+            r["lo"], r["hi"] = (float(b) for b in high.bounds)           # the only bounds ChabrierPrior.lnpdf tests
+            r["p"][0] = (low.mu, 1.0 / low.sigma, -_LOG_ROOT_2PI - math.log(low.sigma) - low.mu - prior.lognorms[0],
+                         high.alpha, np.log(high._C()) - prior.lognorms[1], prior.breakpoint)
+        else:
+            r["kind"] = hc.FEH
+            r["p"][0, :3] = prior.halo_fraction, prior._norm, 1.0 if prior.local else 0.0
+    return r
+
+
+class _Family:
+    """One column's population density: ``names`` of its free parameters, ``ranges`` (their flat hyper-priors) and
+    ``fill(rec, theta)``, which writes the records of the rows ``theta`` [H, len(names)] into ``rec`` [H]."""
+    names = ()
+    ranges = ()
+
+
+class PowerLaw(_Family):
+    """x^alpha on ``bounds`` = (lo, hi), lo > 0, with ``alpha`` free in the range ``alpha`` (its flat hyper-prior);
+    alpha = -1 is normalised by 1 / ln(hi / lo)."""
+    names = ("alpha",)
+
+    def __init__(self, bounds, alpha=(-5.0, 5.0)):
+        self.bounds = (float(bounds[0]), float(bounds[1]))
+        if not 0 < self.bounds[0] < self.bounds[1]:
+            raise ValueError("PowerLaw needs bounds 0 < lo < hi")
+        self.ranges = ((float(alpha[0]), float(alpha[1])),)
+
+    def fill(self, rec, theta):
+        lo, hi = self.bounds
+        a = theta[:, 0]
+        a1 = a + 1.0
+        span = math.log(hi / lo)
+        # ln C = -ln((hi^a1 - lo^a1) / a1) = -(a1 ln lo + ln(expm1(a1 span) / a1)): no cancellation near alpha = -1
+        with np.errstate(all="ignore"):
+            inner = np.where(a1 == 0.0, span, np.expm1(a1 * span) / np.where(a1 == 0.0, 1.0, a1))
+            lnC = -(a1 * math.log(lo) + np.log(inner))
+        rec["kind"], rec["lo"], rec["hi"] = hc.POWERLAW, lo, hi
+        rec["p"][:, 0], rec["p"][:, 1] = lnC, a
+
+
+class TruncatedGaussian(_Family):
+    """A Gaussian renormalised on ``bounds`` = (lo, hi), with ``mean`` and ``sigma`` free in the ranges ``mean`` (default:
+    the bounds) and ``sigma`` (default: (hi - lo) / 1000 to hi - lo)."""
+    names = ("mean", "sigma")
+
+    def __init__(self, bounds, mean=None, sigma=None):
+        self.bounds = lo, hi = (float(bounds[0]), float(bounds[1]))
+        if not (lo < hi and np.isfinite(lo) and np.isfinite(hi)):
+            raise ValueError("TruncatedGaussian needs finite bounds lo < hi")
+        mean = (lo, hi) if mean is None else mean
+        sigma = ((hi - lo) / 1000.0, hi - lo) if sigma is None else sigma
+        if not sigma[0] > 0:
+            raise ValueError("the range of sigma must start above 0")
+        self.ranges = ((float(mean[0]), float(mean[1])), (float(sigma[0]), float(sigma[1])))
+
+    def fill(self, rec, theta):
+        lo, hi = self.bounds
+        mu, sg = theta[:, 0], theta[:, 1]
+        with np.errstate(all="ignore"):
+            a, b = (lo - mu) / sg, (hi - mu) / sg
+            flip = a > 0                                            # take the mass in the lower tail: no 1 - 1
+            a, b = np.where(flip, -b, a), np.where(flip, -a, b)
+            mass = 0.5 * (_erfc(-b / _ROOT2) - _erfc(-a / _ROOT2))
+            c = -_LOG_ROOT_2PI - np.log(sg) - np.log(mass)
+        rec["kind"], rec["lo"], rec["hi"] = hc.TRUNCGAUSS, lo, hi
+        rec["p"][:, 0], rec["p"][:, 1], rec["p"][:, 2], rec["p"][:, 3] = mu, sg, c, 1.0 / sg
+
+
+class Fixed(_Family):
+    """Any device prior as a population density without a free parameter."""
+
+    def __init__(self, prior):
+        self.prior = prior
+        self._rec = prior_record(prior)
+
+    def fill(self, rec, theta):
+        rec[:] = self._rec[0]
+
+
+class PopulationModel:
+    """``PopulationModel(mass=PowerLaw((0.1, 10)), feh=TruncatedGaussian((-4, 0.5)))``: one family per value column, at
+    most four; the density of a star's columns is their product."""
+
+    def __init__(self, **families):
+        if not 1 <= len(families) <= hc.MAX_COLS:
+            raise ValueError("a population model has 1 to %d columns (the kernel's limit)" % hc.MAX_COLS)
+        for col, fam in families.items():
+            if not isinstance(fam, _Family):
+                raise TypeError("the family of %r must be a PowerLaw, TruncatedGaussian or Fixed (got %r)" % (col, fam))
+        self.columns = tuple(families)
+        self.families = tuple(families.values())
+        self.param_names = tuple("%s.%s" % (c, n) for c, f in families.items() for n in f.names)
+        self.ranges = np.array([r for f in self.families for r in f.ranges], dtype=float).reshape(-1, 2)
+
+    @property
+    def n_params(self):
+        return len(self.param_names)
+
+    def pack(self, theta):
+        """``theta`` [H, P] -> records [H, Q] (``_hier_cabi.RECORD``), whole columns at a time."""
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.ndim != 2 or theta.shape[1] != self.n_params:
+            raise ValueError("theta must be [H, %d] (%s)" % (self.n_params, ", ".join(self.param_names)))
+        out = np.zeros((theta.shape[0], len(self.families)), dtype=hc.RECORD)
+        k = 0
+        for q, fam in enumerate(self.families):
+            col = np.zeros(theta.shape[0], dtype=hc.RECORD)
+            fam.fill(col, theta[:, k:k + len(fam.names)])
+            out[:, q] = col
+            k += len(fam.names)
+        return out
+
+    def lnprior(self, theta):
+        """The flat hyper-prior over the free ranges: -sum ln(width) inside, -inf outside; numpy [H]."""
+        theta = np.asarray(theta, dtype=np.float64)
+        if self.n_params == 0:
+            return np.zeros(theta.shape[0])
+        inside = np.all((theta >= self.ranges[:, 0]) & (theta <= self.ranges[:, 1]), axis=1)
+        return np.where(inside, -np.sum(np.log(self.ranges[:, 1] - self.ranges[:, 0])), -np.inf)
+
+
+def _ptr(a):
+    if a is None:
+        return C.c_void_p(0)
+    return C.c_void_p(a.ctypes.data) if isinstance(a, np.ndarray) else dev.ptr(a)
+
+
+class PopulationPosterior:
+    """The posterior of a :class:`PopulationModel`'s hyper-parameters given the stored chains of a fit.
+
+    ``source``: a :class:`~isochrones_amd.sampler.FusedEnsembleSampler` with a stored chain (a catalog's or a single
+    model's), or ``(chain, names)`` - a ``[S, W, T, D]`` chain (CUDA tensor, or a host numpy array, which goes through the
+    library's host entry) and its parameter names.  ``interim``: ``{column: prior}``, the priors the fit used; default: the
+    priors of the model the sampler ran (for the parameter EEP replaces, ``EEPPrior.orig_prior``).  ``mask``: [S], zero for
+    a star to leave out (a failed fit's borrowed walkers); default: the source's ``ok`` flags where it has them."""
+
+    def __init__(self, source, ic, model, interim=None, mask=None, budget_bytes=None):
+        from .sampler import FusedEnsembleSampler
+        self.ic, self.model = ic, model
+        self.budget = HIER_BUDGET_BYTES if budget_bytes is None else int(budget_bytes)
+        template = None
+        if isinstance(source, FusedEnsembleSampler):
+            if source._chain is None:
+                raise ValueError("no stored chain")
+            template = source.target.template if source.is_catalog else source.target
+            if getattr(template, "N", 1) != 1:
+                raise ValueError("the hierarchical likelihood is for single stars (N = 1); this fit has N = %d" % template.N)
+            self.storage, self.S, self.W = source._chain.contiguous(), source.n_ensembles, source.nwalkers
+            names = tuple(template.param_names)
+            if mask is None:
+                mask = getattr(source, "ok", None)
+        else:
+            try:
+                chain, names = source
+            except (TypeError, ValueError):
+                raise ValueError("source must be a FusedEnsembleSampler or (chain [S, W, T, D], parameter names)") from None
+            names = tuple(names)
+            if len(chain.shape) != 4 or chain.shape[3] != len(names):
+                raise ValueError("chain must be [S, W, T, D] with D = %d parameter names" % len(names))
+            self.storage, self.S, self.W, _ = _chain.as_storage(chain)
+        self.host = isinstance(self.storage, np.ndarray)
+        self.storage, self.T, self.D = _chain.check_storage(self.storage, self.S, self.W, _cabi.CHAIN_PARAM_MAJOR,
+                                                            "the hierarchical likelihood takes", host=True)
+        if self.D != len(names):
+            raise ValueError("the chain has %d parameters, %d names" % (self.D, len(names)))
+        self.chain_names = names
+        # where every column is read from
+        self.chain_cols, self.derived_cols = {}, []
+        have = ic.model_grid.interp.column_index if ic is not None else {}
+        for col in model.columns:
+            if col in names:
+                self.chain_cols[col] = names.index(col)
+            elif col in have:
+                if self.host:
+                    raise ValueError("column %r is a model-grid column: it is derived on the device, so the chain must be a "
+                                     "CUDA tensor" % (col,))
+                self.derived_cols.append(col)
+            else:
+                raise ValueError("column %r is neither a parameter of the chain (%s) nor a column of the model grid"
+                                 % (col, ", ".join(names)))
+        # the interim priors
+        if interim is None:
+            if template is None:
+                raise ValueError("a chain without its sampler needs interim={column: prior the fit used}")
+            interim = {}
+            for col in model.columns:
+                if col == "distance" and source.is_catalog:
+                    raise ValueError("a catalog bounds the distance star by star (from its parallax): pass interim= with the "
+                                     "distance prior to reweight from")
+                if col == ic.eep_replaces:
+                    interim[col] = template._priors["eep"].orig_prior
+                elif col in template._priors and col != "eep":
+                    interim[col] = template._priors[col]
+        missing = [c for c in model.columns if c not in interim]
+        if missing:
+            raise ValueError("no interim prior for %s: pass interim={column: prior the fit used}" % ", ".join(missing))
+        for col in model.columns:
+            if _p.is_host_prior(interim[col]):
+                raise ValueError("the interim prior of %r is evaluated on the host; the hierarchical kernel needs one of "
+                                 "isochrones_amd.priors.DEVICE_PRIOR_TYPES" % (col,))
+        self.interim = np.concatenate([prior_record(interim[c]) for c in model.columns])
+        cost = self.T * self.W * 8 * max(1, len(self.derived_cols))
+        self.step = min(self.S, self.budget // cost)
+        if self.step < 1:
+            raise ValueError("the columns of one star take %d bytes, more than budget_bytes = %d: raise the budget or thin "
+                             "the chain" % (cost, self.budget))
+        if mask is not None:
+            mask = mask.detach().cpu().numpy() if dev.is_tensor(mask) else np.asarray(mask)
+            if mask.shape != (self.S,):
+                raise ValueError("mask must be [S] = [%d]" % self.S)
+            mask = np.ascontiguousarray(mask != 0, dtype=np.int32)
+        self.mask = mask
+        self._dev = None            # device copies of the interim records and the mask; the derived chain when it is one slice
+        self._sampler = self._samples = None
+
+    # -- evaluation ---------------------------------------------------------------------------------------------------
+    def _device_state(self):
+        import torch
+        if self._dev is None:
+            device = self.storage.device
+            st = dict(interim=torch.from_numpy(self.interim.view(np.uint8).copy()).to(device),
+                      mask=None if self.mask is None else torch.from_numpy(self.mask).to(device), derived=None)
+            self._dev = st
+        return self._dev
+
+    def _derived(self, s0, n):
+        """The derived chain [T, len(derived_cols), n * W] of the stars [s0, s0 + n); kept when it is the whole catalog."""
+        from . import derived as dv
+        st = self._device_state()
+        whole = s0 == 0 and n == self.S
+        if whole and st["derived"] is not None:
+            return st["derived"]
+        out, _ = dv.derive_storage(self.storage, self.S, self.W, self.ic, tuple(self.derived_cols), ens_begin=s0, n_ens_out=n)
+        if whole:
+            st["derived"] = out
+        return out
+
+    def _columns(self, derived, s0, n):
+        cols = (hc.IsoHierColumn * len(self.model.columns))()
+        for q, col in enumerate(self.model.columns):
+            if col in self.chain_cols:
+                cols[q] = hc.IsoHierColumn(_ptr(self.storage).value, self.D, self.chain_cols[col], self.S, 0)
+            else:
+                cols[q] = hc.IsoHierColumn(_ptr(derived).value, len(self.derived_cols), self.derived_cols.index(col), n, s0)
+        return cols
+
+    def _evaluate(self, theta):
+        """``(L [H], min_ess [H], ell [H, S], ess [H, S], n_bad [S])`` of the rows ``theta`` [H, P]: CUDA tensors for a
+        CUDA tensor ``theta``, numpy arrays otherwise."""
+        as_tensor = dev.is_tensor(theta)
+        th = theta.detach().cpu().numpy() if as_tensor else np.asarray(theta, dtype=np.float64)
+        th = np.atleast_2d(th)
+        rows = self.model.pack(th)
+        H, Q, S = rows.shape[0], rows.shape[1], self.S
+        lib = hc.lib()
+        if self.host:
+            ell, ess = np.empty((H, S)), np.empty((H, S))
+            n_bad, L, mn = np.empty(S, dtype=np.int32), np.empty(H), np.empty(H)
+            interim, mask, drows, fn, stream = self.interim, self.mask, rows, lib.iso_hier_lnlike_host, None
+        else:
+            import torch
+            device = self.storage.device
+            st = self._device_state()
+            f64 = dict(dtype=torch.float64, device=device)
+            ell, ess = torch.empty(H, S, **f64), torch.empty(H, S, **f64)
+            n_bad, L, mn = torch.empty(S, dtype=torch.int32, device=device), torch.empty(H, **f64), torch.empty(H, **f64)
+            interim, mask = st["interim"], st["mask"]
+            drows = torch.from_numpy(np.ascontiguousarray(rows).view(np.uint8).reshape(-1)).to(device)
+            fn, stream = lib.iso_hier_lnlike, dev.stream_ptr(device.index)
+        for s0 in range(0, S, self.step):
+            n = min(self.step, S - s0)
+            last = s0 + n == S
+            derived = self._derived(s0, n) if self.derived_cols else None
+            hc.check(fn(self._columns(derived, s0, n), Q, _cabi.CHAIN_PARAM_MAJOR, self.T, S, self.W, s0, n, _ptr(interim),
+                        _ptr(drows), H, _ptr(mask), _ptr(ell), _ptr(ess), _ptr(n_bad), _ptr(L if last else None),
+                        _ptr(mn if last else None), stream))
+        out = (L, mn, ell, ess, n_bad)
+        if as_tensor and self.host:
+            import torch
+            out = tuple(torch.from_numpy(o).to(theta.device) for o in out)
+        elif not as_tensor and not self.host:
+            out = tuple(o.cpu().numpy() for o in out)
+        return out
+
+    def lnlike(self, theta):
+        """ln L of every row of ``theta`` [H, P]: [H]."""
+        return self._evaluate(theta)[0]
+
+    def min_ess(self, theta):
+        """The smallest effective sample size among the stars, per row: [H].  Below a few, the row's ln L rests on one or two
+        samples of some star and is not to be trusted."""
+        return self._evaluate(theta)[1]
+
+    def star_terms(self, theta):
+        """``(ell [H, S], ess [H, S], n_bad [S])``: every star's term of ln L, its effective sample size under the row, and
+        how many of its samples were bad (NaN, or outside the interim prior).  NaN for a masked star."""
+        return self._evaluate(theta)[2:]
+
+    def lnprior(self, theta):
+        lp = self.model.lnprior(theta.detach().cpu().numpy() if dev.is_tensor(theta) else np.atleast_2d(theta))
+        if dev.is_tensor(theta):
+            import torch
+            return torch.from_numpy(lp).to(theta.device)
+        return lp
+
+    def lnpost(self, theta):
+        """lnprior + lnlike; a row outside the free ranges is -inf (the kernel sees it clipped to the ranges)."""
+        as_tensor = dev.is_tensor(theta)
+        th = np.atleast_2d(theta.detach().cpu().numpy() if as_tensor else np.asarray(theta, dtype=np.float64))
+        lp = self.model.lnprior(th)
+        clipped = np.clip(th, self.model.ranges[:, 0], self.model.ranges[:, 1]) if self.model.n_params else th
+        ll = self._evaluate(clipped)[0]
+        with np.errstate(invalid="ignore"):
+            out = np.where(np.isfinite(lp), lp + ll, -np.inf)
+        out = np.where(np.isnan(out), -np.inf, out)
+        if as_tensor:
+            import torch
+            return torch.from_numpy(out).to(theta.device)
+        return out
+
+    # -- fitting ------------------------------------------------------------------------------------------------------
+    def fit_mcmc(self, nwalkers=64, nburn=200, niter=200, seed=None, p0=None):
+        """Affine-invariant ensemble (framework-op :class:`~isochrones_amd.sampler.EnsembleSampler`) over the
+        hyper-parameters; the walkers of a half-step are the H rows of one ``iso_hier_lnlike`` call.  ``p0`` [nwalkers, P];
+        default: drawn uniformly from the middle half of every free range."""
+        import torch
+        from .sampler import EnsembleSampler
+        P = self.model.n_params
+        if P < 1:
+            raise ValueError("the population model has no free parameter")
+        rng = np.random.default_rng(seed)
+        lo, hi = self.model.ranges[:, 0], self.model.ranges[:, 1]
+        if p0 is None:
+            pos = rng.uniform(lo + 0.25 * (hi - lo), hi - 0.25 * (hi - lo), size=(nwalkers, P))
+            for _ in range(20):
+                bad = ~np.isfinite(self.lnpost(pos))
+                if not bad.any():
+                    break
+                pos[bad] = rng.uniform(lo, hi, size=(int(bad.sum()), P))
+        else:
+            pos = np.asarray(p0, dtype=float)
+        device = torch.device("cpu") if self.host else self.storage.device
+        sampler = EnsembleSampler(nwalkers, P, self.lnpost, seed=int(rng.integers(2 ** 62)), device=device)
+        pos, prob = sampler.run_mcmc(pos, nburn, store=False)
+        sampler.reset()
+        sampler.run_mcmc(pos, niter, lnprob0=prob)
+        self._sampler, self._samples = sampler, None
+        return sampler
+
+    @property
+    def sampler(self):
+        if self._sampler is None:
+            raise AttributeError("fit_mcmc must be run first")
+        return self._sampler
+
+    @property
+    def samples(self):
+        """DataFrame of the hyper-parameters and ``lnprob``."""
+        import pandas as pd
+        if self._samples is None:
+            chain, lnp = self.sampler.flatchain, self.sampler.flatlnprobability
+            self._samples = pd.DataFrame(chain.cpu().numpy(), columns=list(self.model.param_names))
+            self._samples["lnprob"] = lnp.cpu().numpy()
+        return self._samples
