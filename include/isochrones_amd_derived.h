@@ -32,7 +32,9 @@
  * Every operation above is one IEEE float64 operation, rounded on its own, in the order written; there is no fused
  * multiply-add anywhere (the library is built with -ffp-contract=off and writes no fma).  A sample's values therefore
  * do not depend on the batch it is in, on the ensemble range or on the chain layout, and this is the arithmetic of the
- * interpolator (oracle/iso_oracle.c, orc_interp_value) term by term.
+ * interpolator (oracle/iso_oracle.c, orc_interp_value) term by term.  The kernel, the host entry and the libraries of
+ * isochrones_amd_predict.h and isochrones_amd_population.h compile one statement of this cell (the internal
+ * csrc/common/grid_interp.h), so one table and one point give the same bits in all of them.
  *
  * Output.  out[(t * (C * Q) + c * Q + q) * R + r]: parameter-major storage [nsteps][C * Q][R] of n_ens_out ensembles,
  * which iso_chain_quantiles_layout takes with n_params = C * Q.  nan_count[e * (C * Q) + c * Q + q], e < n_ens_out

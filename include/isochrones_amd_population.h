@@ -45,7 +45,9 @@
  *      sys_A[b]   = sys_mag[b] - (-2.5 * log10((0.0 + pow(10, -0.4 * (mag_0[b] - A_0[b]))) + pow(10, -0.4 * (m1 - a1))))
  * so an absent or off-grid secondary leaves the primary's light and a NaN primary gives NaN.
  * log10 and pow are the math library's of the side that runs (device or host), so a magnitude or an extinction of the
- * kernel and one of the host entry may differ in the last bits; the model columns are the same bits on both sides.
+ * kernel and one of the host entry may differ in the last bits; the model columns are the same bits on both sides, and
+ * the bits iso_derived_chain gives for the same table and point (steps 1 and 2 are one statement, the internal
+ * csrc/common/grid_interp.h, compiled for both kernels and both host entries).
  *
  * Outputs, float64, structure-of-arrays with i fastest, every one skipped when its pointer is null:
  *   cols_out[(c * Q + q) * N + i]   value[q] of component c

@@ -43,7 +43,8 @@
  *   6. term j (band b: j = b; Teff, logg, feh, parallax: j = B .. B + 3), present when obs_val[j] is not NaN:
  *      d = obs_val[j] - model[j], z_j = (d * d) / (obs_unc[j] * obs_unc[j]).
  * log10 and pow are the math library's of the side that runs (device or host), so a magnitude of the kernel and one of the
- * host entry may differ in the last bits; everything else is the same sequence of operations on both sides.
+ * host entry may differ in the last bits; everything else is the same sequence of operations on both sides (steps 1 and
+ * 2 are one statement, the internal csrc/common/grid_interp.h, compiled for the kernel and for the host entry).
  * A sample is bad when the model value of any present term is not finite.  Bad samples enter no mean and are counted.
  *
  * Means and their summation order.  The samples of one ensemble are numbered s = t * W + walker, 0 <= s < nsteps * W.

@@ -7,7 +7,8 @@
  * For one query (x0, x1, target) let g(k) be the trilinear interpolation of the column at (x0, x1, axk[k]), with the
  * interpolator's own rules: a query on a node takes the cell above it (the last node: the cell below, weight 1), every
  * corner of the cell is multiplied by its weight even when that weight is zero (a NaN neighbour gives NaN), a NaN or
- * out-of-axis coordinate gives NaN.  The search range is the intersection of the [first, last] finite ranges of the four
+ * out-of-axis coordinate gives NaN (the bracket and the on-axis rule are the lines the other grid libraries compile, the
+ * internal csrc/common/grid_cell.h).  The search range is the intersection of the [first, last] finite ranges of the four
  * corner columns.  With k* the smallest index of the range with g(k*) >= target:
  *
  *   k* is the first index of the range and g(k*) == target          axk[k*]

@@ -5,6 +5,7 @@ from __future__ import annotations
 import ctypes as C
 
 from ._cabi import IsoError  # noqa: F401  (callers catch it as _population_cabi.IsoError)
+from ._predict_cabi import BC_TABLE_FIELDS
 from ._sidelib import SideLibrary
 
 ERR_INVALID = -1
@@ -24,10 +25,8 @@ class IsoPopulationModelTable(C.Structure):
 
 
 class IsoPopulationBcTable(C.Structure):
-    """``iso_population_bc_table``: B band columns packed ``[nT][ng][nf][nA][B]`` and the four axes."""
-    _fields_ = [("bc", C.c_void_p), ("axT", C.c_void_p), ("axg", C.c_void_p), ("axf", C.c_void_p), ("axA", C.c_void_p),
-                ("nT", C.c_int32), ("ng", C.c_int32), ("nf", C.c_int32), ("nA", C.c_int32), ("B", C.c_int32),
-                ("reserved", C.c_int32)]
+    """``iso_population_bc_table``: the same fields as ``iso_predict_bc_table``."""
+    _fields_ = BC_TABLE_FIELDS
 
 
 class IsoPopulationOut(C.Structure):

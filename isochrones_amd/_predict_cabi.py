@@ -22,11 +22,16 @@ class IsoPredictModelTable(C.Structure):
                 ("n0", C.c_int32), ("n1", C.c_int32), ("nk", C.c_int32), ("reserved", C.c_int32)]
 
 
+#: a BC table of the C ABI (this library's and libiso_population.so's): B band columns packed ``[nT][ng][nf][nA][B]`` and
+#: the four axes
+BC_TABLE_FIELDS = [("bc", C.c_void_p), ("axT", C.c_void_p), ("axg", C.c_void_p), ("axf", C.c_void_p), ("axA", C.c_void_p),
+                   ("nT", C.c_int32), ("ng", C.c_int32), ("nf", C.c_int32), ("nA", C.c_int32), ("B", C.c_int32),
+                   ("reserved", C.c_int32)]
+
+
 class IsoPredictBcTable(C.Structure):
-    """``iso_predict_bc_table``: B band columns packed ``[nT][ng][nf][nA][B]`` and the four axes."""
-    _fields_ = [("bc", C.c_void_p), ("axT", C.c_void_p), ("axg", C.c_void_p), ("axf", C.c_void_p), ("axA", C.c_void_p),
-                ("nT", C.c_int32), ("ng", C.c_int32), ("nf", C.c_int32), ("nA", C.c_int32), ("B", C.c_int32),
-                ("reserved", C.c_int32)]
+    """``iso_predict_bc_table``."""
+    _fields_ = BC_TABLE_FIELDS
 
 
 class IsoPredictOut(C.Structure):

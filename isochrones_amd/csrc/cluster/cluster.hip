@@ -14,22 +14,15 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include "isochrones_amd_cluster.h"
+#include "../common/last_error.h"
 
 namespace {
 
 constexpr int TILE = 64;          // stars per workgroup = lanes of one wave
 constexpr int FINISH = 256;       // threads of the per-row finishing workgroup
-
-thread_local char g_err[256];
-
-int fail(int rc, const char* msg) {
-    snprintf(g_err, sizeof g_err, "%s", msg);
-    return rc;
-}
 
 // the reference's logaddexp (cluster_utils.py): xmax + log(exp(x1 - xmax) + exp(x2 - xmax)).  One of the two exponentials
 // is exp(0) = 1 exactly, so only the other is evaluated; the sum is the same double.  ln 0 = -inf on one side selects

@@ -1,12 +1,13 @@
 // A stored ensemble chain as the libraries that post-process it see it (csrc/diag/, csrc/derived/, csrc/predict/): the
-// strides of its two layouts, a component's packed parameter indices, the checks on its shape with their messages, and the
-// library's last error.  Internal, no part of any ABI, and of internal linkage: each library has its own last error.
+// strides of its two layouts, a component's packed parameter indices and the checks on its shape with their messages; it
+// brings the library's last error (last_error.h) with it.  Internal, no part of any ABI, and of internal linkage.
 #ifndef ISO_COMMON_CHAIN_VIEW_H
 #define ISO_COMMON_CHAIN_VIEW_H
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
+
+#include "last_error.h"
 
 namespace {
 
@@ -53,18 +54,6 @@ inline const char* chain_shape_error(int checks, const ChainShape& s) {
         for (int c = 0; c < s.C * 3; ++c)
             if (s.comps[c] < 0 || s.comps[c] >= s.ndim) return "a component's parameter index is outside [0, ndim)";
     return nullptr;
-}
-
-thread_local char g_err[256];
-
-int fail(int rc, const char* msg) {
-    snprintf(g_err, sizeof g_err, "%s", msg);
-    return rc;
-}
-
-int fail(int rc, const char* who, const char* why) {            // "<entry point>: <what is wrong>"
-    snprintf(g_err, sizeof g_err, "%s: %s", who, why);
-    return rc;
 }
 
 }  // namespace

@@ -1,6 +1,8 @@
-// Where a coordinate sits on a grid axis, for the libraries that interpolate along a stored chain (csrc/derived/,
-// csrc/predict/; csrc/diag/ takes qnan()).  include/isochrones_amd_derived.h defines it and the order of the arithmetic: a
-// value is the same bits in these libraries, kernel and host statement, because they compile these lines.  Internal.
+// Where a coordinate sits on a grid axis: the bracket, the on-axis rule and the NaN of every library that reads a packed
+// grid.  csrc/solve/ includes it directly; csrc/derived/, csrc/predict/ and csrc/population/ through grid_interp.h, which
+// builds the cells on it; csrc/diag/ and csrc/hier/ take qnan().  include/isochrones_amd_derived.h defines the bracket: an
+// index and a fraction are the same bits in these libraries, kernel and host entry, because they compile these lines.
+// Internal.
 #ifndef ISO_COMMON_GRID_CELL_H
 #define ISO_COMMON_GRID_CELL_H
 

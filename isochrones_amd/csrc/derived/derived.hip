@@ -18,7 +18,7 @@
 
 #include "isochrones_amd_derived.h"
 #include "../common/chain_view.h"
-#include "../common/grid_cell.h"
+#include "../common/grid_interp.h"
 
 namespace {
 
@@ -42,26 +42,9 @@ struct Args {
 constexpr int FRESH01 = 1 << 24;
 
 template <int Q>
-__device__ __forceinline__ void corner(const double* __restrict__ p, double w, double (&v)[Q]) {
-    if constexpr (Q % 2 == 0) {
-        const double2* __restrict__ p2 = reinterpret_cast<const double2*>(p);
-#pragma unroll
-        for (int j = 0; j < Q / 2; ++j) {
-            const double2 d = p2[j];
-            v[2 * j] = v[2 * j] + d.x * w;
-            v[2 * j + 1] = v[2 * j + 1] + d.y * w;
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < Q; ++j) v[j] = v[j] + p[j] * w;
-    }
-}
-
-template <int Q>
 __device__ __forceinline__ void derive(const Args& A) {
     const iso_derived_table& T = A.T;
     const int R = A.R, CQ = A.C * Q;
-    const int sk = Q, s1 = T.nk * Q, s0 = T.n1 * T.nk * Q;     // corner steps along axk, ax1, ax0 in doubles
     for (int item = blockIdx.x; item < A.items; item += gridDim.x) {
         const int t = item / A.chunks;
         const int r = (item - t * A.chunks) * BLOCK + (int)threadIdx.x;
@@ -84,21 +67,11 @@ __device__ __forceinline__ void derive(const Args& A) {
             const bool ok = ok01 && on_axis(T.axk, T.nk, xk);
             double v[Q];
             if (ok) {
-                int ik;
-                double tk;
+                int ik, off[8];
+                double tk, w[8];
                 bracket(T.axk, T.nk, xk, ik, tk);
-                const double u0 = 1 - t0, u1 = 1 - t1, uk = 1 - tk;
-                const double* __restrict__ p = T.cols + ((i0 * T.n1 + i1) * T.nk + ik) * Q;
-#pragma unroll
-                for (int j = 0; j < Q; ++j) v[j] = 0.0;
-                corner<Q>(p, (u0 * u1) * uk, v);
-                corner<Q>(p + sk, (u0 * u1) * tk, v);
-                corner<Q>(p + s1, (u0 * t1) * uk, v);
-                corner<Q>(p + s1 + sk, (u0 * t1) * tk, v);
-                corner<Q>(p + s0, (t0 * u1) * uk, v);
-                corner<Q>(p + s0 + sk, (t0 * u1) * tk, v);
-                corner<Q>(p + s0 + s1, (t0 * t1) * uk, v);
-                corner<Q>(p + s0 + s1 + sk, (t0 * t1) * tk, v);
+                cell3_corners(T.n1, T.nk, Q, t0, t1, tk, off, w);
+                cell3_columns<Q, Q % 2 == 0>(T.cols + ((i0 * T.n1 + i1) * T.nk + ik) * Q, off, w, v);
             } else {
 #pragma unroll
                 for (int j = 0; j < Q; ++j) v[j] = qnan();
@@ -222,23 +195,7 @@ int iso_derived_chain_host(const iso_derived_table* table, const double* chain, 
                 const double x0 = row[comp_p0(comp) * A.st.st_d], x1 = row[comp_p1(comp) * A.st.st_d],
                              xk = row[comp_pk(comp) * A.st.st_d];
                 double v[ISO_DERIVED_MAX_COLS];
-                if (on_axis(T.ax0, T.n0, x0) && on_axis(T.ax1, T.n1, x1) && on_axis(T.axk, T.nk, xk)) {
-                    int i[3];
-                    double tt[3];
-                    bracket(T.ax0, T.n0, x0, i[0], tt[0]);
-                    bracket(T.ax1, T.n1, x1, i[1], tt[1]);
-                    bracket(T.axk, T.nk, xk, i[2], tt[2]);
-                    for (int q = 0; q < Q; ++q) v[q] = 0.0;
-                    for (int j = 0; j < 8; ++j) {
-                        const int b0 = (j >> 2) & 1, b1 = (j >> 1) & 1, bk = j & 1;
-                        const double f0 = b0 ? tt[0] : 1 - tt[0], f1 = b1 ? tt[1] : 1 - tt[1], fk = bk ? tt[2] : 1 - tt[2];
-                        const double w = (f0 * f1) * fk;
-                        const double* p = T.cols + ((((int64_t)i[0] + b0) * T.n1 + i[1] + b1) * T.nk + i[2] + bk) * Q;
-                        for (int q = 0; q < Q; ++q) v[q] = v[q] + p[q] * w;
-                    }
-                } else {
-                    for (int q = 0; q < Q; ++q) v[q] = qnan();
-                }
+                cell3(T, Q, x0, x1, xk, v);
                 for (int q = 0; q < Q; ++q) {
                     out[(t * CQ + c * Q + q) * R + r] = v[q];
                     if (v[q] != v[q]) ++nan_count[(int64_t)(r / W) * CQ + c * Q + q];

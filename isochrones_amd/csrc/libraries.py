@@ -23,7 +23,7 @@ CLUSTER = KernelLibrary(
     name="cluster", flags=_NO_CONTRACT,
     #: every kernel the library compiles (tests/test_cluster_library.py pins this set)
     kernels=("k_cluster_finish", "k_cluster_pairs"),
-    max_vgpr=256, min_waves=2)
+    max_vgpr=256, min_waves=2, extra_headers=("common/last_error.h",))
 
 # nested sampling of a catalog (csrc/nested/).  Its kernels include libiso_hip.so's header-only device code
 # (iso_fast_kernel.h: lnpost_wave and what it needs), so those headers are part of its source digest.
@@ -54,10 +54,12 @@ SOLVE = KernelLibrary(
     kernels=("k_solve_last_axis",),
     #: the kernel is a chain of dependent gathers: its throughput is occupancy, so the register budget is the 8-waves-per-SIMD
     #: one, 64 VGPRs; the wave gate itself is the two per SIMD every library has at least
-    max_vgpr=64, min_waves=2)
+    max_vgpr=64, min_waves=2, extra_headers=("common/grid_cell.h", "common/last_error.h"))
 
-#: shared by the three libraries that post-process a stored chain (internal; named outright: a missing one stops the digest)
-_CHAIN_HEADERS = ("common/grid_cell.h", "common/chain_view.h")
+#: shared by the libraries that post-process a stored chain (internal; named outright: a missing one stops the digest)
+_CHAIN_HEADERS = ("common/grid_cell.h", "common/chain_view.h", "common/last_error.h")
+#: the same for the two that interpolate grid cells along it (grid_interp.h: the cell the population library shares)
+_CELL_HEADERS = _CHAIN_HEADERS + ("common/grid_interp.h",)
 
 # per-star chain convergence diagnostics (csrc/diag/)
 # -ffp-contract=off: the compiler fuses nothing on its own; the kernel's fused multiply-adds are the ones written as fma(),
@@ -77,10 +79,10 @@ DERIVED = KernelLibrary(
     name="derived", flags=_NO_CONTRACT,
     #: every kernel the library compiles (tests/test_derived_library.py pins this set)
     kernels=("k_derived_chain",),
-    #: k_derived_chain compiles to 118 VGPRs, no scratch and 4 waves per SIMD: the eight-column branch keeps 8 accumulators and
+    #: k_derived_chain compiles to 120 VGPRs, no scratch and 4 waves per SIMD: the eight-column branch keeps 8 accumulators and
     #: the cell's corner loads in flight (16 two-double loads a sample; they are what hides the gather latency).  Forcing 8 waves
     #: (64 VGPRs) spills to scratch, so the budget is the 4-waves-per-SIMD one: 128 VGPRs, and no scratch at all
-    max_vgpr=128, min_waves=4, extra_headers=_CHAIN_HEADERS)
+    max_vgpr=128, min_waves=4, extra_headers=_CELL_HEADERS)
 
 # the posterior-predictive check of a stored chain (csrc/predict/)
 # -ffp-contract=off: the compiler fuses nothing, and the sources write no fma(): every product and every sum of the header's
@@ -89,11 +91,11 @@ PREDICT = KernelLibrary(
     name="predict", flags=_NO_CONTRACT,
     #: every kernel the library compiles (tests/test_predict_library.py pins this set)
     kernels=("k_predict_chain",),
-    #: k_predict_chain compiles to 239 VGPRs, no scratch and 2 waves per SIMD.  A sample holds the brackets and weights of a 4-D
+    #: k_predict_chain compiles to 242 VGPRs, no scratch and 2 waves per SIMD.  A sample holds the brackets and weights of a 4-D
     #: cell, eight band accumulators, four corners of eight bands in flight and the model cell's 32 values; the call's 60-odd
     #: uniform values (two tables, strides, outputs) are staged in LDS because as kernel arguments they overflow the SGPR file and
     #: their spill slots count as scratch.  The workgroup is two waves, so the budget is the 2-waves-per-SIMD one: 256 VGPRs
-    max_vgpr=256, min_waves=2, extra_headers=_CHAIN_HEADERS)
+    max_vgpr=256, min_waves=2, extra_headers=_CELL_HEADERS)
 
 # a batch of coeval single or binary systems evaluated on the model and the BC grid (csrc/population/)
 # -ffp-contract=off: the compiler fuses nothing, and the sources write no fma(): every product and every sum of the header's
@@ -109,7 +111,7 @@ POPULATION = KernelLibrary(
     #: 4 waves (128 VGPRs) it spills 190 registers to scratch, with four bands a pass still 94; so the budget is the
     #: 2-waves-per-SIMD one: 256 VGPRs, and no scratch at all.  Its uniform arguments (two tables, eight pointers) overflow
     #: the SGPR file into VGPR lanes, not into scratch, so they are not staged in LDS as k_predict_chain's are
-    max_vgpr=256, min_waves=2, extra_headers=("common/grid_cell.h",))
+    max_vgpr=256, min_waves=2, extra_headers=("common/grid_cell.h", "common/grid_interp.h", "common/last_error.h"))
 
 # the hierarchical (population) likelihood from the stored chains of a catalog (csrc/hier/)
 # -ffp-contract=off: the compiler fuses nothing, and the sources write no fma(): every product and every sum of the header's

@@ -16,10 +16,10 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "isochrones_amd_population.h"
-#include "../common/grid_cell.h"
+#include "../common/grid_interp.h"
+#include "../common/last_error.h"
 
 namespace {
 
@@ -40,34 +40,10 @@ struct Args {
     int32_t C;
 };
 
-thread_local char g_err[256];
-
-int fail(int rc, const char* who, const char* why) {            // "<entry point>: <what is wrong>"
-    snprintf(g_err, sizeof g_err, "%s: %s", who, why);
-    return rc;
-}
-
 __host__ __device__ inline double pos_inf() {
     union { uint64_t u; double d; } x;
     x.u = 0x7ff0000000000000ULL;
     return x.d;
-}
-
-// one corner of W adjacent columns into the accumulators
-template <int W, bool PAIR>
-__device__ __forceinline__ void corner(const double* __restrict__ p, double w, double (&v)[W]) {
-    if constexpr (PAIR) {
-        const double2* __restrict__ p2 = reinterpret_cast<const double2*>(p);
-#pragma unroll
-        for (int j = 0; j < W / 2; ++j) {
-            const double2 d = p2[j];
-            v[2 * j] = v[2 * j] + d.x * w;
-            v[2 * j + 1] = v[2 * j + 1] + d.y * w;
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < W; ++j) v[j] = v[j] + p[j] * w;
-    }
 }
 
 // The columns [q0, q0 + W) of one component: interpolated (p: the cell's first corner at column q0; off[j], w[j]: the
@@ -78,10 +54,7 @@ __device__ __forceinline__ void column_group(const iso_population_model_table& M
                                              int64_t N, double (&hv)[4]) {
     double v[W];
     if (ok) {
-#pragma unroll
-        for (int j = 0; j < W; ++j) v[j] = 0.0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) corner<W, PAIR>(p + off[k], w[k], v);
+        cell3_columns<W, PAIR>(p, off, w, v);
     } else {
 #pragma unroll
         for (int j = 0; j < W; ++j) v[j] = qnan();
@@ -127,23 +100,10 @@ __global__ void __launch_bounds__(BLOCK) k_population_eval(const Args A) {
         for (int c = 0; c < C; ++c) {
             const double* __restrict__ x = A.coords + (int64_t)c * 3 * N + i;
             const double x0 = x[0], x1 = x[N], xk = x[2 * N];
-            const bool ok = on_axis(M.ax0, M.n0, x0) && on_axis(M.ax1, M.n1, x1) && on_axis(M.axk, M.nk, xk);
-            int i0, i1, ik;
-            double t0, t1, tk;
-            bracket(M.ax0, M.n0, x0, i0, t0);
-            bracket(M.ax1, M.n1, x1, i1, t1);
-            bracket(M.axk, M.nk, xk, ik, tk);
-            const double u0 = 1 - t0, u1 = 1 - t1, uk = 1 - tk;
-            const int sk = Q, s1 = M.nk * Q, s0 = M.n1 * M.nk * Q;
+            const bool ok = on_grid3(M, x0, x1, xk);
             int off[8];
             double w[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int b0 = (k >> 2) & 1, b1 = (k >> 1) & 1, bk = k & 1;
-                off[k] = b0 * s0 + b1 * s1 + bk * sk;
-                w[k] = ((b0 ? t0 : u0) * (b1 ? t1 : u1)) * (bk ? tk : uk);
-            }
-            const double* __restrict__ p = M.cols + ((i0 * M.n1 + i1) * M.nk + ik) * Q;
+            const double* __restrict__ p = M.cols + cell3_at(M, Q, x0, x1, xk, off, w);
             double* __restrict__ o = A.O.cols_out ? A.O.cols_out + (int64_t)c * Q * N + i : nullptr;
             double hv[4] = {0.0, 0.0, 0.0, 0.0};
             int q0 = 0;
@@ -176,7 +136,6 @@ __global__ void __launch_bounds__(BLOCK) k_population_eval(const Args A) {
         bracket(T.axA, T.nA, av, iA, tA);
         bracket(T.axA, T.nA, 0.0, iA0, tA0);
         const double uA = 1 - tA, uA0 = 1 - tA0;
-        const int sf = T.nA * B, sg = T.nf * sf, sT = T.ng * sg;
         for (int b0 = 0; b0 < B; b0 += CH) {
             const int nb = B - b0 < CH ? B - b0 : CH;
             double sum[CH], sumt[CH];                           // the two sums of the system (C = 2)
@@ -185,25 +144,19 @@ __global__ void __launch_bounds__(BLOCK) k_population_eval(const Args A) {
             for (int c = 0; c < C; ++c) {
                 const double xT = c == 0 ? hv0[0] : hv1[0], xg = c == 0 ? hv0[1] : hv1[1];
                 const double xf = c == 0 ? hv0[2] : hv1[2], mbol = c == 0 ? hv0[3] : hv1[3];
-                const bool okb = on_axis(T.axT, T.nT, xT) && on_axis(T.axg, T.ng, xg) && on_axis(T.axf, T.nf, xf);
+                const bool okb = bc_on_grid(T, xT, xg, xf);
                 double acc[CH], acc0[CH];
 #pragma unroll
                 for (int j = 0; j < CH; ++j) acc[j] = acc0[j] = 0.0;
                 if (okb) {
-                    int iT, ig, jf;
-                    double tT, tg, tf;
-                    bracket(T.axT, T.nT, xT, iT, tT);
-                    bracket(T.axg, T.ng, xg, ig, tg);
-                    bracket(T.axf, T.nf, xf, jf, tf);
-                    const double uT = 1 - tT, ug = 1 - tg, uf = 1 - tf;
-                    const double* __restrict__ pb = T.bc + ((iT * T.ng + ig) * T.nf + jf) * sf + b0;
+                    const BcCell cell = bc_bracket(T, xT, xg, xf);
+                    const double* __restrict__ pb = T.bc + cell.node + b0;
                     // corner order 0000 .. 1111 with bA fastest: the three slow bits as a loop, whose (T, g, f) weight both
                     // lookups share
 #pragma nounroll
                     for (int k = 0; k < 8; ++k) {
-                        const int bT = (k >> 2) & 1, bg = (k >> 1) & 1, bf = k & 1;
-                        const double wTgf = ((bT ? tT : uT) * (bg ? tg : ug)) * (bf ? tf : uf);
-                        const double* __restrict__ pk = pb + bT * sT + bg * sg + bf * sf;
+                        const double wTgf = bc_weight(cell, k);
+                        const double* __restrict__ pk = pb + bc_offset(T, k);
 #pragma unroll
                         for (int bA = 0; bA < 2; ++bA) {
                             const double wa = wTgf * (bA ? tA : uA), wa0 = wTgf * (bA ? tA0 : uA0);
@@ -321,50 +274,16 @@ void component_host(const Args& A, int64_t i, int c, double* v, double* mag, dou
     const int64_t N = A.N;
     const double x0 = A.coords[((int64_t)c * 3 + 0) * N + i], x1 = A.coords[((int64_t)c * 3 + 1) * N + i],
                  xk = A.coords[((int64_t)c * 3 + 2) * N + i];
-    if (on_axis(M.ax0, M.n0, x0) && on_axis(M.ax1, M.n1, x1) && on_axis(M.axk, M.nk, xk)) {
-        int ii[3];
-        double tt[3];
-        bracket(M.ax0, M.n0, x0, ii[0], tt[0]);
-        bracket(M.ax1, M.n1, x1, ii[1], tt[1]);
-        bracket(M.axk, M.nk, xk, ii[2], tt[2]);
-        for (int q = 0; q < Q; ++q) v[q] = 0.0;
-        for (int j = 0; j < 8; ++j) {
-            const int b0 = (j >> 2) & 1, b1 = (j >> 1) & 1, bk = j & 1;
-            const double f0 = b0 ? tt[0] : 1 - tt[0], f1 = b1 ? tt[1] : 1 - tt[1], fk = bk ? tt[2] : 1 - tt[2];
-            const double w = (f0 * f1) * fk;
-            const double* p = M.cols + ((((int64_t)ii[0] + b0) * M.n1 + ii[1] + b1) * M.nk + ii[2] + bk) * Q;
-            for (int q = 0; q < Q; ++q) v[q] = v[q] + p[q] * w;
-        }
-    } else {
-        for (int q = 0; q < Q; ++q) v[q] = qnan();
-    }
-    const double xs[4] = {v[M.hot[0]], v[M.hot[1]], v[M.hot[2]], 0.0}, mbol = v[M.hot[3]];
-    const double* axes[4] = {T.axT, T.axg, T.axf, T.axA};
-    const int ns[4] = {T.nT, T.ng, T.nf, T.nA};
-    const double dm = 5 * log10(A.distance[i] / 10.0), base = mbol + dm;
+    cell3(M, Q, x0, x1, xk, v);
+    const double mbol = v[M.hot[3]], dm = 5 * log10(A.distance[i] / 10.0), base = mbol + dm;
     double val[2][ISO_POPULATION_MAX_BANDS];                    // bc_c at AV, bc0_c at 0.0
-    for (int pass = 0; pass < 2; ++pass) {
-        const double xA = pass == 0 ? A.AV[i] : 0.0;
-        bool ok = on_axis(axes[3], ns[3], xA);
-        int ii[4];
-        double tt[4];
-        for (int d = 0; d < 3; ++d) {
-            ok = ok && on_axis(axes[d], ns[d], xs[d]);
-            bracket(axes[d], ns[d], xs[d], ii[d], tt[d]);
+    for (int pass = 0; pass < 2; ++pass)
+        for (int b0 = 0; b0 < B; b0 += CH) {
+            double chunk[CH];
+            const int nb = B - b0 < CH ? B - b0 : CH;
+            bc_chunk<CH>(T, v[M.hot[0]], v[M.hot[1]], v[M.hot[2]], pass == 0 ? A.AV[i] : 0.0, b0, nb, chunk);
+            for (int j = 0; j < nb; ++j) val[pass][b0 + j] = chunk[j];
         }
-        bracket(axes[3], ns[3], xA, ii[3], tt[3]);
-        for (int b = 0; b < B; ++b) val[pass][b] = ok ? 0.0 : qnan();
-        if (!ok) continue;
-        for (int j = 0; j < 16; ++j) {
-            const int bT = (j >> 3) & 1, bg = (j >> 2) & 1, bf = (j >> 1) & 1, bA = j & 1;
-            const double fT = bT ? tt[0] : 1 - tt[0], fg = bg ? tt[1] : 1 - tt[1], ff = bf ? tt[2] : 1 - tt[2],
-                         fA = bA ? tt[3] : 1 - tt[3];
-            const double w = ((fT * fg) * ff) * fA;
-            const double* p =
-                T.bc + (((((int64_t)ii[0] + bT) * T.ng + ii[1] + bg) * T.nf + ii[2] + bf) * T.nA + ii[3] + bA) * B;
-            for (int b = 0; b < B; ++b) val[pass][b] = val[pass][b] + p[b] * w;
-        }
-    }
     for (int b = 0; b < B; ++b) {
         mag[b] = base - val[0][b];
         const double tru = base - val[1][b];

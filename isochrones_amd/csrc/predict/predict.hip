@@ -18,7 +18,7 @@
 
 #include "isochrones_amd_predict.h"
 #include "../common/chain_view.h"
-#include "../common/grid_cell.h"
+#include "../common/grid_interp.h"
 
 namespace {
 
@@ -46,68 +46,6 @@ struct Args {
 
 __host__ __device__ inline bool finite_(double x) { return x - x == 0.0; }
 
-// step 1 of the header: (Teff, logg, feh, Mbol) at (x0, x1, xk)
-__host__ __device__ inline void model4(const iso_predict_model_table& M, double x0, double x1, double xk, double (&v)[4]) {
-    if (!(on_axis(M.ax0, M.n0, x0) && on_axis(M.ax1, M.n1, x1) && on_axis(M.axk, M.nk, xk))) {
-        v[0] = v[1] = v[2] = v[3] = qnan();
-        return;
-    }
-    int i0, i1, ik;
-    double t0, t1, tk;
-    bracket(M.ax0, M.n0, x0, i0, t0);
-    bracket(M.ax1, M.n1, x1, i1, t1);
-    bracket(M.axk, M.nk, xk, ik, tk);
-    const double u0 = 1 - t0, u1 = 1 - t1, uk = 1 - tk;
-    const int sk = 4, s1 = M.nk * 4, s0 = M.n1 * M.nk * 4;
-    const double* __restrict__ p = M.cols + ((i0 * M.n1 + i1) * M.nk + ik) * 4;
-    v[0] = v[1] = v[2] = v[3] = 0.0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int b0 = (j >> 2) & 1, b1 = (j >> 1) & 1, bk = j & 1;
-        const double w = ((b0 ? t0 : u0) * (b1 ? t1 : u1)) * (bk ? tk : uk);
-        const double* __restrict__ c = p + b0 * s0 + b1 * s1 + bk * sk;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = v[q] + c[q] * w;
-    }
-}
-
-// step 2 of the header for the bands [b0, b0 + nb), nb <= CH
-__host__ __device__ inline void bc_chunk(const iso_predict_bc_table& T, double xT, double xg, double xf, double xA, int b0,
-                                         int nb, double (&v)[CH]) {
-    if (!(on_axis(T.axT, T.nT, xT) && on_axis(T.axg, T.ng, xg) && on_axis(T.axf, T.nf, xf) && on_axis(T.axA, T.nA, xA))) {
-#pragma unroll
-        for (int j = 0; j < CH; ++j) v[j] = qnan();
-        return;
-    }
-    int iT, ig, jf, iA;
-    double tT, tg, tf, tA;
-    bracket(T.axT, T.nT, xT, iT, tT);
-    bracket(T.axg, T.ng, xg, ig, tg);
-    bracket(T.axf, T.nf, xf, jf, tf);
-    bracket(T.axA, T.nA, xA, iA, tA);
-    const double uT = 1 - tT, ug = 1 - tg, uf = 1 - tf, uA = 1 - tA;
-    const int sA = T.B, sf = T.nA * T.B, sg = T.nf * sf, sT = T.ng * sg;
-    const double* __restrict__ p = T.bc + (((iT * T.ng + ig) * T.nf + jf) * T.nA + iA) * T.B + b0;
-#pragma unroll
-    for (int j = 0; j < CH; ++j) v[j] = 0.0;
-    // corner order 0000 .. 1111 with bA fastest: the two slow bits as loops (four corners of eight bands in flight at a time)
-#pragma nounroll
-    for (int k = 0; k < 4; ++k) {
-        const int bT = k >> 1, bg = k & 1;
-        const double wTg = (bT ? tT : uT) * (bg ? tg : ug);
-        const double* __restrict__ c0 = p + bT * sT + bg * sg;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const int bf = m >> 1, bA = m & 1;
-            const double w = (wTg * (bf ? tf : uf)) * (bA ? tA : uA);
-            const double* __restrict__ c = c0 + bf * sf + bA * sA;
-#pragma unroll
-            for (int j = 0; j < CH; ++j)
-                if (j < nb) v[j] = v[j] + c[j] * w;
-        }
-    }
-}
-
 // steps 1 to 5 for one sample and the bands [b0, b0 + nb): the system magnitudes and component 0's (Teff, logg, feh).
 // wk[j * ws], j < 2 * CH: working space of a multiple system (the kernel's is LDS: pow and log10 then run in loops over
 // the bands instead of eight unrolled copies held in registers)
@@ -122,8 +60,8 @@ __host__ __device__ inline void sample_chunk(const Args& A, const double* __rest
         const double x0 = row[comp_p0(comp) * A.st.st_d], x1 = row[comp_p1(comp) * A.st.st_d],
                      xk = row[comp_pk(comp) * A.st.st_d];
         double v[4], bcv[CH];
-        model4(A.M, x0, x1, xk, v);
-        bc_chunk(A.T, v[0], v[1], v[2], av, b0, nb, bcv);
+        cell3(A.M, 4, x0, x1, xk, v);                           // step 1 of the header: (Teff, logg, feh, Mbol)
+        bc_chunk<CH>(A.T, v[0], v[1], v[2], av, b0, nb, bcv);   // step 2
         if (c == 0) {
             spec[0] = v[0];
             spec[1] = v[1];

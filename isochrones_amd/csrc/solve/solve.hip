@@ -15,37 +15,14 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "isochrones_amd_solve.h"
+#include "../common/grid_cell.h"
+#include "../common/last_error.h"
 
 namespace {
 
 constexpr int BLOCK = 256;
-
-thread_local char g_err[256];
-
-int fail(int rc, const char* msg) {
-    snprintf(g_err, sizeof g_err, "%s", msg);
-    return rc;
-}
-
-__device__ __forceinline__ double d_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-// searchsorted + find_indices of the interpolator: i = largest index with ax[i] <= x, clamped to n - 2 (the last node
-// belongs to the cell below it, t = 1).  Precondition: ax[0] <= x <= ax[n-1].
-__device__ __forceinline__ void bracket(const double* __restrict__ ax, int n, double x, int& i, double& t) {
-    int base = 0, len = n;
-    while (len > 1) {
-        const int half = len >> 1;
-        base = (ax[base + half] <= x) ? base + half : base;
-        len -= half;
-    }
-    base = min(base, n - 2);
-    const double lo = ax[base], hi = ax[base + 1];
-    i = base;
-    t = (x - lo) / (hi - lo);
-}
 
 struct Corners {
     double w00, w01, w10, w11;      // weights over (ax0, ax1)
@@ -82,11 +59,8 @@ __global__ void __launch_bounds__(BLOCK) k_solve_last_axis(const iso_solve_table
     if (q >= n) return;
     const double a = x0[q], b = x1[q], y = target[q];
     const int n0 = T.n0, n1 = T.n1, nk = T.nk;
-    double e = d_nan();
-    // NaN first, then the bounds test, as the interpolator; a NaN target has no k*
-    const bool inside = a == a && b == b && y == y && !(a < T.ax0[0]) && !(a > T.ax0[n0 - 1]) && !(b < T.ax1[0]) &&
-                        !(b > T.ax1[n1 - 1]);
-    if (inside) {
+    double e = qnan();
+    if (on_axis(T.ax0, n0, a) && on_axis(T.ax1, n1, b) && y == y) {     // a NaN target has no k*
         int i, j;
         double t0, t1;
         bracket(T.ax0, n0, a, i, t0);
@@ -136,7 +110,7 @@ __global__ void __launch_bounds__(BLOCK) k_solve_last_axis(const iso_solve_table
                 }
             }
         } else {
-            double prev = d_nan();
+            double prev = qnan();
             for (int k = F; k <= L; ++k) {
                 const double g = g_full(col, c, k, nk);
                 if (g >= y) {

@@ -9,9 +9,9 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
+import functools
 
-from . import _cabi, _chain, _derived_cabi, device as dev
+from . import _cabi, _chain, _derived_cabi, _tables, device as dev
 
 #: what ``derived=True`` asks for in a catalog fit, as far as the model grid has the column and the fit does not sample it
 DEFAULT_PROPS = ("mass", "radius", "age", "Teff", "logg")
@@ -80,15 +80,11 @@ class DerivedTable:
     """Up to 8 columns of a model grid packed ``[n0, n1, nk, Q]`` on a device with its axes, and the ``iso_derived_table``
     that points at them."""
 
-    def __init__(self, grid, icols, axes, device):
+    def __init__(self, interp, icols, device):
         self.device = device
-        packed = np.ascontiguousarray(grid[..., list(icols)], dtype=np.float64)
-        self.cols = dev.to_device_f64(packed, device)
-        self.axes = [dev.to_device_f64(a, device) for a in axes]
-        n0, n1, nk, Q = packed.shape
-        self.Q = Q
-        self.table = _derived_cabi.IsoDerivedTable(self.cols.data_ptr(), self.axes[0].data_ptr(), self.axes[1].data_ptr(),
-                                                   self.axes[2].data_ptr(), n0, n1, nk, Q)
+        self.cols, self.axes, shape = _tables.pack_model(interp, icols, functools.partial(dev.to_device_f64, device=device))
+        self.Q = shape[3]
+        self.table = _tables.fill(_derived_cabi.IsoDerivedTable, self.cols, self.axes, shape)
 
 
 def derived_tables(ic, columns, device):
@@ -97,7 +93,7 @@ def derived_tables(ic, columns, device):
     dfi, M = ic.model_grid.interp, _derived_cabi.MAX_COLS
     icols = [dfi.column_index[c] for c in columns]
     return _chain.cached_by_generation(ic, "_derived_tables", (device, tuple(columns)), dfi._handles.generation, lambda: [
-        DerivedTable(dfi.grid, icols[i:i + M], dfi.index_columns, device) for i in range(0, len(icols), M)])
+        DerivedTable(dfi, icols[i:i + M], device) for i in range(0, len(icols), M)])
 
 
 def derive_storage(storage, n_ens, nwalkers, ic, props, N=1, layout=_cabi.CHAIN_PARAM_MAJOR, ens_begin=0, n_ens_out=None):

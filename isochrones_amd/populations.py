@@ -12,7 +12,7 @@ import re
 
 import numpy as np
 
-from . import _chain, _population_cabi, device as dev
+from . import _chain, _population_cabi, _tables, device as dev
 from .priors import ChabrierPrior, FehPrior, PowerLawPrior
 
 #: how often ``StarPopulation.generate(exact_N=True)`` redraws the rows that fell off the grid before it gives up
@@ -124,21 +124,15 @@ class PopulationTables:
     of the BC grid packed ``[nT, ng, nf, nA, B]`` where a backend keeps its arrays, with their axes and the two structs."""
 
     def __init__(self, ic, cols, bands, backend):
-        m, b = ic.model_grid.interp, ic.bc_grid.interp
+        m = ic.model_grid.interp
         names = list(m.columns)
         icols = [names.index(c) for c in cols]
-        self.cols = backend.array(np.ascontiguousarray(m.grid[..., icols], dtype=np.float64))
-        self.axes = [backend.array(a) for a in m.index_columns]
-        bcols = [int(i) for i in ic._band_cols(list(bands))]
-        self.bc = backend.array(np.ascontiguousarray(b.grid[..., bcols], dtype=np.float64))
-        self.bc_axes = [backend.array(a) for a in b.index_columns]
-        n0, n1, nk = m.grid.shape[:3]
-        nT, ng, nf, nA = b.grid.shape[:4]
-        self.Q, self.B = len(icols), len(bcols)
+        self.cols, self.axes, shape = _tables.pack_model(m, icols, backend.array)
+        self.bc, self.bc_axes, bshape = _tables.pack_bc(ic, bands, backend.array)
+        self.Q, self.B = shape[3], bshape[4]
         hot = (C.c_int32 * 4)(*[icols.index(int(i)) for i in ic._cols])
-        p = lambda a: backend.ptr(a).value                                      # noqa: E731
-        self.model = _population_cabi.IsoPopulationModelTable(p(self.cols), *[p(a) for a in self.axes], n0, n1, nk, self.Q, hot)
-        self.bct = _population_cabi.IsoPopulationBcTable(p(self.bc), *[p(a) for a in self.bc_axes], nT, ng, nf, nA, self.B, 0)
+        self.model = _tables.fill(_population_cabi.IsoPopulationModelTable, self.cols, self.axes, shape, hot)
+        self.bct = _tables.fill(_population_cabi.IsoPopulationBcTable, self.bc, self.bc_axes, bshape, 0)
 
 
 def population_tables(ic, cols, bands, backend):
@@ -161,17 +155,6 @@ def _packed_columns(ic, props):
     if len(packed) > _population_cabi.MAX_COLS:
         raise ValueError("at most %d model columns per call (the hot four included), got %d" % (_population_cabi.MAX_COLS, len(packed)))
     return cols, packed
-
-
-def _check_bands(ic, bands):
-    bands = tuple(ic.bands if bands is None else ((bands,) if isinstance(bands, str) else bands))
-    if not 1 <= len(bands) <= _population_cabi.MAX_BANDS:
-        raise ValueError("1 to %d bands per call, got %d" % (_population_cabi.MAX_BANDS, len(bands)))
-    have = list(ic.bc_grid.interp.columns)
-    for b in bands:
-        if b not in have:
-            raise ValueError("the bolometric-correction grid has no band %r" % (b,))
-    return bands
 
 
 def column_names(cols, bands):
@@ -220,7 +203,7 @@ def _evaluate(ic, mass_A, mass_B, age, feh, distance, AV, bands, props, accurate
         ic = ic.track
     if getattr(ic, "eep_replaces", None) != "age":
         raise NotImplementedError("populations need the evolution-track parametrisation")
-    bands = _check_bands(ic, bands)
+    bands = _tables.check_bands(ic, bands, _population_cabi.MAX_BANDS)
     cols, packed = _packed_columns(ic, props)
     if accurate not in (False, True, "exact"):
         raise ValueError("accurate is False, True or 'exact'")

@@ -10,7 +10,9 @@ import ctypes as C
 
 import numpy as np
 
-from . import _cabi, _chain, _predict_cabi, derived as dv, device as dev
+import functools
+
+from . import _cabi, _chain, _predict_cabi, _tables, derived as dv, device as dev
 
 #: the terms after the bands, in the kernel's order
 SPEC_TERMS = ("Teff", "logg", "feh", "parallax")
@@ -97,18 +99,12 @@ class PredictTables:
     ``[nT, ng, nf, nA, B]`` on a device, with their axes and the two structs that point at them."""
 
     def __init__(self, ic, bands, device):
-        m, b = ic.model_grid.interp, ic.bc_grid.interp
-        self.cols = dev.to_device_f64(np.ascontiguousarray(m.grid[..., list(ic._cols)], dtype=np.float64), device)
-        self.axes = [dev.to_device_f64(a, device) for a in m.index_columns]
-        bcols = [int(i) for i in ic._band_cols(list(bands))]
-        self.bc = dev.to_device_f64(np.ascontiguousarray(b.grid[..., bcols], dtype=np.float64), device)
-        self.bc_axes = [dev.to_device_f64(a, device) for a in b.index_columns]
-        n0, n1, nk = m.grid.shape[:3]
-        nT, ng, nf, nA = b.grid.shape[:4]
-        self.B = len(bcols)
-        self.model = _predict_cabi.IsoPredictModelTable(self.cols.data_ptr(), *[a.data_ptr() for a in self.axes], n0, n1, nk, 0)
-        self.bct = _predict_cabi.IsoPredictBcTable(self.bc.data_ptr(), *[a.data_ptr() for a in self.bc_axes], nT, ng, nf, nA,
-                                                   self.B, 0)
+        put = functools.partial(dev.to_device_f64, device=device)
+        self.cols, self.axes, shape = _tables.pack_model(ic.model_grid.interp, ic._cols, put)
+        self.bc, self.bc_axes, bshape = _tables.pack_bc(ic, bands, put)
+        self.B = bshape[4]
+        self.model = _tables.fill(_predict_cabi.IsoPredictModelTable, self.cols, self.axes, shape[:3], 0)
+        self.bct = _tables.fill(_predict_cabi.IsoPredictBcTable, self.bc, self.bc_axes, bshape, 0)
 
 
 def predict_tables(ic, bands, device):
@@ -119,17 +115,6 @@ def predict_tables(ic, bands, device):
                                        lambda: PredictTables(ic, bands, device))
 
 
-def _check_bands(ic, bands):
-    bands = tuple(ic.bands if bands is None else ((bands,) if isinstance(bands, str) else bands))
-    if not 1 <= len(bands) <= _predict_cabi.MAX_BANDS:
-        raise ValueError("1 to %d bands per call, got %d" % (_predict_cabi.MAX_BANDS, len(bands)))
-    have = list(ic.bc_grid.interp.columns)
-    for b in bands:
-        if b not in have:
-            raise ValueError("the bolometric-correction grid has no band %r" % (b,))
-    return bands
-
-
 def predict_storage(storage, lnprob, n_ens, nwalkers, ic, bands, obs, N=1, layout=_cabi.CHAIN_PARAM_MAJOR, ens_begin=0,
                     n_ens_out=None, want_mags=True):
     """The posterior-predictive check of the ensembles ``[ens_begin, ens_begin + n_ens_out)`` of a stored chain.
@@ -138,7 +123,7 @@ def predict_storage(storage, lnprob, n_ens, nwalkers, ic, bands, obs, N=1, layou
     None (then no MAP); ``obs``: see :func:`pack_obs`, rows indexed by the ensemble.  Returns a :class:`PredictiveResult` on
     the current stream, without a synchronise.  One ``iso_predict_chain`` launch."""
     import torch
-    bands = _check_bands(ic, bands)
+    bands = _tables.check_bands(ic, bands, _predict_cabi.MAX_BANDS)
     comps = dv.components(ic, N)
     n_ens, W = int(n_ens), int(nwalkers)
     x, nsteps, ndim = _chain.check_storage(storage, n_ens, W, layout, "the posterior-predictive check takes")

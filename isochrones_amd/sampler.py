@@ -363,11 +363,11 @@ class FusedEnsembleSampler:
         ``iso_predict_chain`` launch on the parameter-major storage and summarised by one ``iso_chain_quantiles_layout`` call
         where it lies.  A band of an ensemble with a NaN sample (off either grid) has NaN quantiles."""
         import torch
-        from . import _chain, predictive as pv
+        from . import _chain, _predict_cabi, _tables, predictive as pv
         if self._chain is None:
             raise ValueError("no stored chain")
         budget = pv.PREDICT_BUDGET_BYTES if budget_bytes is None else int(budget_bytes)
-        bands = pv._check_bands(ic, bands)
+        bands = _tables.check_bands(ic, bands, _predict_cabi.MAX_BANDS)
         B = len(bands)
         nsteps, S, W = int(self._chain.shape[0]), self.n_ensembles, self.nwalkers
         packed = pv.pack_obs(obs, bands, S)

@@ -11,7 +11,9 @@ import ctypes as C
 
 import numpy as np
 
-from . import _solve_cabi, device as dev
+import functools
+
+from . import _solve_cabi, _tables, device as dev
 from .interp import HOST_CALL_ROWS
 
 
@@ -48,12 +50,9 @@ class DeviceTable:
     def __init__(self, col, axes, ranges, device):
         import torch
         self.device = device
-        self.col = dev.to_device_f64(col, device)
-        self.axes = [dev.to_device_f64(a, device) for a in axes]
+        self.col, self.axes, shape = _tables.pack_grid(col, axes, functools.partial(dev.to_device_f64, device=device))
         self.ranges = torch.as_tensor(np.ascontiguousarray(ranges, dtype=np.int32), device=torch.device("cuda", device))
-        n0, n1, nk = col.shape
-        self.table = _solve_cabi.IsoSolveTable(self.col.data_ptr(), self.axes[0].data_ptr(), self.axes[1].data_ptr(),
-                                               self.axes[2].data_ptr(), self.ranges.data_ptr(), n0, n1, nk)
+        self.table = _tables.fill(_solve_cabi.IsoSolveTable, self.col, self.axes + [self.ranges], shape)
 
     def solve_device(self, x0, x1, target):
         """Contiguous float64 CUDA tensors of equal length on this device -> CUDA tensor, on the current stream."""

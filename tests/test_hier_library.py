@@ -92,7 +92,7 @@ def test_build_lists():
     assert len({s.source_digest() for s in every}) == len(every)
     assert not any("hier" in os.path.basename(s) for s in main.sources())
     assert os.path.exists(B.HEADER) and B.HEADER in B.headers()
-    assert [os.path.basename(h) for h in B.headers()] == ["isochrones_amd_hier.h", "grid_cell.h", "chain_view.h"]
+    assert [os.path.basename(h) for h in B.headers()] == ["isochrones_amd_hier.h", "grid_cell.h", "chain_view.h", "last_error.h"]
     # what build() iterates, and what git ignores
     entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
     assert "libraries.BUILD_ORDER + libraries.ADDED" in entry

@@ -79,7 +79,7 @@ def test_build_order_is_all_and_the_new_library():
     assert len({s.source_digest() for s in libraries.BUILD_ORDER}) == len(libraries.BUILD_ORDER)
     assert not any("population" in os.path.basename(s) for s in main.sources())
     assert os.path.exists(B.HEADER) and B.HEADER in B.headers()
-    assert [os.path.basename(h) for h in B.headers()] == ["isochrones_amd_population.h", "grid_cell.h"]
+    assert [os.path.basename(h) for h in B.headers()] == ["isochrones_amd_population.h", "grid_cell.h", "grid_interp.h", "last_error.h"]
     # what build() and the command line iterate
     entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
     assert "libraries.BUILD_ORDER" in entry and "libraries.ALL" not in entry
