@@ -25,5 +25,7 @@ from .populations import (StarPopulation, BinaryDistribution, StarFormationHisto
                           evaluate_binaries)
 from . import hierarchical
 from .hierarchical import PopulationModel, PopulationPosterior, PowerLaw, TruncatedGaussian, Fixed
+from . import selection
+from .selection import InjectionSet
 
 __version__ = "0.1.0"

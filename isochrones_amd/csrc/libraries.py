@@ -1,9 +1,9 @@
 """The side libraries, each a spec for sidelib.KernelLibrary, in the order __graft_entry__.build() builds them
-(BUILD_ORDER + ADDED).
+(BUILD_ORDER + ADDED + NEWER).
 
     python -m isochrones_amd.csrc.libraries NAME [--force] [--verbose]
 
-A new library is one more spec here (and its name in ADDED), its sources in csrc/<name>/ and its header
+A new library is one more spec here (and its name in NEWER), its sources in csrc/<name>/ and its header
 include/isochrones_amd_<name>.h."""
 from __future__ import annotations
 
@@ -127,6 +127,22 @@ HIER = KernelLibrary(
     #: VGPRs, and no scratch at all.  k_hier_total is 17 VGPRs at 8 waves
     max_vgpr=168, min_waves=3, extra_headers=_CHAIN_HEADERS)
 
+# the detectable fraction of a population density from an injection set (csrc/select/): the selection term of HIER's
+# likelihood.  It reads HIER's records (its header includes isochrones_amd_hier.h) and evaluates them through
+# common/family_lnf.h, the family arithmetic of hier.hip restated for the libraries after it
+# -ffp-contract=off: the compiler fuses nothing, and the sources write no fma(): every product and every sum of the header's
+# definition is rounded on its own (a row is bit-identical alone, in any tiling of the hyper rows and on every call)
+SELECT = KernelLibrary(
+    name="select", flags=_NO_CONTRACT,
+    #: every kernel the library compiles (tests/test_select_library.py pins this set)
+    kernels=("k_select_partial", "k_select_total"),
+    #: k_select_partial is k_hier_stars's loop over a chunk of injections instead of a star's samples: 152 VGPRs, no
+    #: scratch, 3.1 KB of LDS and 3 waves per SIMD, for the same reason (the accumulators of eight rows, eight inlined
+    #: family evaluations); the budget is the 3-waves-per-SIMD one: 168 VGPRs, and no scratch at all.  k_select_total is
+    #: 44 VGPRs at 8 waves
+    max_vgpr=168, min_waves=3,
+    extra_headers=("../../include/isochrones_amd_hier.h", "common/family_lnf.h", "common/grid_cell.h", "common/last_error.h"))
+
 #: the six libraries the shared builder started with (tests/test_side_libraries_cpu.py pins this tuple to exactly these)
 ALL = (CLUSTER, NESTED, SOLVE, DIAG, DERIVED, PREDICT)
 #: what __graft_entry__.build() and the command line below build, in order: ALL and the libraries added since ALL was
@@ -135,10 +151,14 @@ BUILD_ORDER = ALL + (POPULATION,)
 #: the libraries added after BUILD_ORDER was pinned in its turn (tests/test_population_library.py); __graft_entry__.build()
 #: and the command line below go through BUILD_ORDER + ADDED.  The next library goes here
 ADDED = (HIER,)
+#: the libraries added after ADDED was pinned in its turn (tests/test_hier_library.py); __graft_entry__.build() and the
+#: command line below go through BUILD_ORDER + ADDED + NEWER.  The next library goes here: its test asserts membership,
+#: not equality, so this tuple grows
+NEWER = (SELECT,)
 
 
 if __name__ == "__main__":
-    by_name = {spec.name: spec for spec in BUILD_ORDER + ADDED}
+    by_name = {spec.name: spec for spec in BUILD_ORDER + ADDED + NEWER}
     names = [a for a in sys.argv[1:] if not a.startswith("--")]
     if len(names) != 1 or names[0] not in by_name:
         sys.exit("usage: python -m isochrones_amd.csrc.libraries {%s} [--force] [--verbose]" % ",".join(by_name))

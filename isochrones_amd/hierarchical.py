@@ -12,7 +12,10 @@ model's EEP prior is stated in (``EEPPrior`` interpolates ``(mass, dm_deep)``). 
 fit's priors are stated in - the prior of the parameter EEP replaces is ``EEPPrior.orig_prior`` of that coordinate, the
 Jacobian d(orig)/d(EEP) belongs to the change of variables - so no Jacobian enters.
 
-Selection effects, densities that couple columns (mixtures across columns) and multiple systems (N > 1) are out of scope."""
+Selection effects (a magnitude-limited catalog) are corrected from an injection set: ``PopulationPosterior(...,
+injections=)`` and :mod:`isochrones_amd.selection`; without one the likelihood assumes that every star of the population
+could have entered the catalog.  Densities that couple columns (mixtures across columns) and multiple systems (N > 1) are
+out of scope."""
 from __future__ import annotations
 
 import ctypes as C
@@ -203,9 +206,15 @@ class PopulationPosterior:
     model's), or ``(chain, names)`` - a ``[S, W, T, D]`` chain (CUDA tensor, or a host numpy array, which goes through the
     library's host entry) and its parameter names.  ``interim``: ``{column: prior}``, the priors the fit used; default: the
     priors of the model the sampler ran (for the parameter EEP replaces, ``EEPPrior.orig_prior``).  ``mask``: [S], zero for
-    a star to leave out (a failed fit's borrowed walkers); default: the source's ``ok`` flags where it has them."""
+    a star to leave out (a failed fit's borrowed walkers); default: the source's ``ok`` flags where it has them.
 
-    def __init__(self, source, ic, model, interim=None, mask=None, budget_bytes=None):
+    ``injections``: an :class:`~isochrones_amd.selection.InjectionSet` that holds every column of ``model`` with its draw
+    prior.  With it ``lnlike`` is ``L - S_unmasked * ln_alpha`` (``ln_alpha``: the log of the fraction of the row's
+    population that the survey detects; -inf where that estimate is zero), and ``lnpost`` is -inf for a row whose
+    ``selection_neff`` is below ``min_neff_factor * S_unmasked`` (Farr 2019).  The set is moved once to where the chain
+    lies; a host chain goes through the library's host entry.  Without it nothing changes."""
+
+    def __init__(self, source, ic, model, interim=None, mask=None, budget_bytes=None, injections=None, min_neff_factor=4.0):
         from .sampler import FusedEnsembleSampler
         self.ic, self.model = ic, model
         self.budget = HIER_BUDGET_BYTES if budget_bytes is None else int(budget_bytes)
@@ -283,6 +292,12 @@ class PopulationPosterior:
         self.mask = mask
         self._dev = None            # device copies of the interim records and the mask; the derived chain when it is one slice
         self._sampler = self._samples = None
+        self.n_unmasked = self.S if mask is None else int(mask.sum())
+        self.min_neff_factor = float(min_neff_factor)
+        self.injections, self.selection = injections, None
+        if injections is not None:
+            from .selection import Selection
+            self.selection = Selection(injections, model, None if self.host else self.storage.device)
 
     # -- evaluation ---------------------------------------------------------------------------------------------------
     def _device_state(self):
@@ -353,9 +368,46 @@ class PopulationPosterior:
             out = tuple(o.cpu().numpy() for o in out)
         return out
 
+    def _alpha(self, theta):
+        """``(ln_alpha [H], n_eff [H])`` from the injection set, like :meth:`_evaluate`'s results."""
+        if self.selection is None:
+            raise ValueError("this posterior has no injection set (injections=)")
+        as_tensor = dev.is_tensor(theta)
+        th = np.atleast_2d(theta.detach().cpu().numpy() if as_tensor else np.asarray(theta, dtype=np.float64))
+        la, ne, _ = self.selection.alpha(th)
+        if as_tensor and self.host:
+            import torch
+            la, ne = (torch.from_numpy(o).to(theta.device) for o in (la, ne))
+        elif not as_tensor and not self.host:
+            la, ne = (o.cpu().numpy() for o in (la, ne))
+        return la, ne
+
+    def _selected(self, theta):
+        """``(L - S_unmasked * ln_alpha [H], n_eff [H])``.  A row whose estimate of alpha is zero (no detected injection
+        in its support) is -inf."""
+        la, ne = self._alpha(theta)
+        L = self._evaluate(theta)[0]
+        if dev.is_tensor(L):
+            import torch
+            ll = torch.where(torch.isneginf(la), la, L - self.n_unmasked * la)
+        else:
+            with np.errstate(invalid="ignore"):
+                ll = np.where(np.isneginf(la), -np.inf, L - self.n_unmasked * la)
+        return ll, ne
+
     def lnlike(self, theta):
-        """ln L of every row of ``theta`` [H, P]: [H]."""
-        return self._evaluate(theta)[0]
+        """ln L of every row of ``theta`` [H, P]: [H]; with an injection set, corrected for the selection."""
+        if self.selection is None:
+            return self._evaluate(theta)[0]
+        return self._selected(theta)[0]
+
+    def ln_alpha(self, theta):
+        """The log of the detectable fraction of every row's population, from the injection set: [H]."""
+        return self._alpha(theta)[0]
+
+    def selection_neff(self, theta):
+        """The effective number of injections behind every row's ``ln_alpha``: [H]."""
+        return self._alpha(theta)[1]
 
     def min_ess(self, theta):
         """The smallest effective sample size among the stars, per row: [H].  Below a few, the row's ln L rests on one or two
@@ -380,7 +432,11 @@ class PopulationPosterior:
         th = np.atleast_2d(theta.detach().cpu().numpy() if as_tensor else np.asarray(theta, dtype=np.float64))
         lp = self.model.lnprior(th)
         clipped = np.clip(th, self.model.ranges[:, 0], self.model.ranges[:, 1]) if self.model.n_params else th
-        ll = self._evaluate(clipped)[0]
+        if self.selection is None:
+            ll = self._evaluate(clipped)[0]
+        else:
+            ll, neff = self._selected(clipped)
+            ll = np.where(neff < self.min_neff_factor * self.n_unmasked, -np.inf, ll)
         with np.errstate(invalid="ignore"):
             out = np.where(np.isfinite(lp), lp + ll, -np.inf)
         out = np.where(np.isnan(out), -np.inf, out)
