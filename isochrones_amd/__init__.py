@@ -25,6 +25,7 @@ from .populations import (StarPopulation, BinaryDistribution, StarFormationHisto
                           evaluate_binaries)
 from . import hierarchical
 from .hierarchical import PopulationModel, PopulationPosterior, PowerLaw, TruncatedGaussian, Fixed
+from . import reweight
 from . import selection
 from .selection import InjectionSet
 

@@ -143,6 +143,27 @@ SELECT = KernelLibrary(
     max_vgpr=168, min_waves=3,
     extra_headers=("../../include/isochrones_amd_hier.h", "common/family_lnf.h", "common/grid_cell.h", "common/last_error.h"))
 
+# the population-informed posterior of every star from its stored chain (csrc/reweight/): per-sample weights under the hyper
+# rows of a fitted population, and weighted per-star summaries.  It reads HIER's records and columns (its header includes
+# isochrones_amd_hier.h), evaluates them through common/family_lnf.h and takes HIER's ell as the weights' normaliser
+# -ffp-contract=off: the compiler fuses nothing, and the sources write no fma(): every product and every sum of the header's
+# definition is rounded on its own (a star's outputs are bit-identical alone, in any batch, star range and layout)
+REWEIGHT = KernelLibrary(
+    name="reweight", flags=_NO_CONTRACT,
+    #: every kernel the library compiles (tests/test_reweight_library.py pins this set)
+    kernels=("k_reweight_summary", "k_reweight_weights"),
+    #: k_reweight_weights compiles to 101 VGPRs, no scratch, 19 KB of LDS (a tile of 64 rows' records) and 4 waves per SIMD.
+    #: A lane holds the sample's four columns with their logs and interim terms (24 registers) and one inlined family
+    #: evaluation, the FEH one with three exp and a log in flight; the rows run innermost into one accumulator, so
+    #: k_hier_stars's 48 registers of per-row sums are gone.  The column index is a run-time loop over select chains: unrolled,
+    #: its four independent family evaluations interleave to 232 VGPRs (2 waves).  Its 49 spilled SGPRs (the argument block)
+    #: go to VGPR lanes, not to scratch.  Held to 5 waves (96 VGPRs) it spills 2 registers to scratch; the per-(row, sample)
+    #: exp binds, not latency, so the budget is the 4-waves-per-SIMD one: 128 VGPRs, and no scratch at all.
+    #: k_reweight_summary (16 bins of a radix pass in registers) is 59 VGPRs at 8 waves
+    max_vgpr=128, min_waves=4,
+    extra_headers=("../../include/isochrones_amd_hier.h", "common/family_lnf.h", "common/chain_view.h", "common/grid_cell.h",
+                   "common/last_error.h"))
+
 #: the six libraries the shared builder started with (tests/test_side_libraries_cpu.py pins this tuple to exactly these)
 ALL = (CLUSTER, NESTED, SOLVE, DIAG, DERIVED, PREDICT)
 #: what __graft_entry__.build() and the command line below build, in order: ALL and the libraries added since ALL was
@@ -154,7 +175,7 @@ ADDED = (HIER,)
 #: the libraries added after ADDED was pinned in its turn (tests/test_hier_library.py); __graft_entry__.build() and the
 #: command line below go through BUILD_ORDER + ADDED + NEWER.  The next library goes here: its test asserts membership,
 #: not equality, so this tuple grows
-NEWER = (SELECT,)
+NEWER = (SELECT, REWEIGHT)
 
 
 if __name__ == "__main__":

@@ -12,6 +12,9 @@ model's EEP prior is stated in (``EEPPrior`` interpolates ``(mass, dm_deep)``). 
 fit's priors are stated in - the prior of the parameter EEP replaces is ``EEPPrior.orig_prior`` of that coordinate, the
 Jacobian d(orig)/d(EEP) belongs to the change of variables - so no Jacobian enters.
 
+What the fitted population says about the individual stars (their posteriors with the population in place of the
+interim prior) is :meth:`PopulationPosterior.star_posteriors` (:mod:`isochrones_amd.reweight`).
+
 Selection effects (a magnitude-limited catalog) are corrected from an injection set: ``PopulationPosterior(...,
 injections=)`` and :mod:`isochrones_amd.selection`; without one the likelihood assumes that every star of the population
 could have entered the catalog.  Densities that couple columns (mixtures across columns) and multiple systems (N > 1) are
@@ -418,6 +421,26 @@ class PopulationPosterior:
         """``(ell [H, S], ess [H, S], n_bad [S])``: every star's term of ln L, its effective sample size under the row, and
         how many of its samples were bad (NaN, or outside the interim prior).  NaN for a masked star."""
         return self._evaluate(theta)[2:]
+
+    def star_posteriors(self, theta=None, columns=None, q=(0.5, 0.16, 0.84), as_tensors=False):
+        """Every star's posterior once the population replaces the interim prior (:mod:`isochrones_amd.reweight`; the
+        kernels of libiso_reweight.so on the chain where it lies).  ``theta`` [H, P]: rows taken as equally weighted draws
+        of the hyper posterior; default: at most 64 rows spread evenly over the samples of :meth:`fit_mcmc`, which must
+        have run.  ``columns``: chain parameters or model-grid columns (derived on the device), model columns or not;
+        default: the chain's parameters, then the model's derived columns.  ``q``: 1 to 8 probabilities.  Returns a
+        DataFrame (``as_tensors=True``: a dict of tensors where the chain lies) with one row per star: per column
+        ``{col}_median, _p16, _p84`` (``_q<100 p>`` for another q), ``{col}_mean``, ``{col}_sd``, then ``ess`` (the effective
+        sample size of the star's weights) and ``n_bad``.  A masked star is NaN; so are the column summaries of a star with
+        no weight left (its ``ess`` is 0)."""
+        from . import reweight
+        return reweight.star_posteriors(self, theta, columns, q, as_tensors)
+
+    def star_weights(self, theta=None, stars=None):
+        """The weights behind :meth:`star_posteriors`, ``[n, W * T]`` with sample ``m = t * W + w``, normalised to sum 1 per
+        star, for weighted plots of one's own.  ``stars``: an index, a sequence of indices or a contiguous slice; default:
+        all.  On the chain's device (numpy for a host chain)."""
+        from . import reweight
+        return reweight.star_weights(self, theta, stars)
 
     def lnprior(self, theta):
         lp = self.model.lnprior(theta.detach().cpu().numpy() if dev.is_tensor(theta) else np.atleast_2d(theta))
