@@ -28,5 +28,7 @@ from .hierarchical import PopulationModel, PopulationPosterior, PowerLaw, Trunca
 from . import reweight
 from . import selection
 from .selection import InjectionSet
+from . import relations
+from .relations import LinearGaussian
 
 __version__ = "0.1.0"

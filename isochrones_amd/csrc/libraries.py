@@ -164,6 +164,27 @@ REWEIGHT = KernelLibrary(
     extra_headers=("../../include/isochrones_amd_hier.h", "common/family_lnf.h", "common/chain_view.h", "common/grid_cell.h",
                    "common/last_error.h"))
 
+# HIER's likelihood for a population density that links columns (csrc/relation/): a column's Gaussian follows another column
+# linearly, so its truncation normaliser is per (hyper row, sample) and is evaluated in the kernel.  It reads HIER's records
+# and columns (its header includes isochrones_amd_hier.h) and evaluates the kinds 1 .. 8 through common/family_lnf.h, the
+# linked kind through common/relation_lnf.h
+# -ffp-contract=off: the compiler fuses nothing, and the sources write no fma(): every product and every sum of the header's
+# definition is rounded on its own (a star's row is bit-identical alone, in any batch and in any tiling of the hyper rows,
+# and equal to HIER's where no record is linked)
+RELATION = KernelLibrary(
+    name="relation", flags=_NO_CONTRACT,
+    #: every kernel the library compiles (tests/test_relation_library.py pins this set)
+    kernels=("k_relation_stars", "k_relation_total"),
+    #: k_relation_stars compiles to 205 VGPRs, no scratch, 3.4 KB of LDS and 2 waves per SIMD: k_hier_stars's 153 (the sums of
+    #: eight rows, eight inlined family evaluations) and on top the sample's four values, kept for the parents, and the linked
+    #: term with two erfc and a log in flight.  A row tile of 4 compiles to 165 VGPRs and 3 waves and was measured slower (72.9
+    #: against 68.3 ms): the per-sample work is shared by half as many rows.  So the budget is the
+    #: 2-waves-per-SIMD one: 256 VGPRs, and no scratch at all.  Its 43 spilled SGPRs (the argument block) go to VGPR lanes, not
+    #: to scratch.  k_relation_total is k_hier_total: 17 VGPRs at 8 waves
+    max_vgpr=256, min_waves=2,
+    extra_headers=("../../include/isochrones_amd_hier.h", "common/relation_lnf.h", "common/family_lnf.h",
+                   "common/chain_view.h", "common/grid_cell.h", "common/last_error.h"))
+
 #: the six libraries the shared builder started with (tests/test_side_libraries_cpu.py pins this tuple to exactly these)
 ALL = (CLUSTER, NESTED, SOLVE, DIAG, DERIVED, PREDICT)
 #: what __graft_entry__.build() and the command line below build, in order: ALL and the libraries added since ALL was
@@ -175,7 +196,7 @@ ADDED = (HIER,)
 #: the libraries added after ADDED was pinned in its turn (tests/test_hier_library.py); __graft_entry__.build() and the
 #: command line below go through BUILD_ORDER + ADDED + NEWER.  The next library goes here: its test asserts membership,
 #: not equality, so this tuple grows
-NEWER = (SELECT, REWEIGHT)
+NEWER = (SELECT, REWEIGHT, RELATION)
 
 
 if __name__ == "__main__":

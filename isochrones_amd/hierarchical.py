@@ -17,8 +17,14 @@ interim prior) is :meth:`PopulationPosterior.star_posteriors` (:mod:`isochrones_
 
 Selection effects (a magnitude-limited catalog) are corrected from an injection set: ``PopulationPosterior(...,
 injections=)`` and :mod:`isochrones_amd.selection`; without one the likelihood assumes that every star of the population
-could have entered the catalog.  Densities that couple columns (mixtures across columns) and multiple systems (N > 1) are
-out of scope."""
+could have entered the catalog.
+
+A density that links one column to another (:class:`isochrones_amd.relations.LinearGaussian`: [Fe/H] against age) makes the
+model *coupled*: its truncation normaliser differs for every (hyper row, sample), so the likelihood goes through the kernels
+of libiso_relation.so (``iso_relation_lnlike``, include/isochrones_amd_relation.h), which evaluate it where the sample is.
+A coupled model takes no injection set and gives no per-star posteriors yet.  A mixture across columns needs no kernel (the
+mean weight is linear in the density: ``logsumexp_k(ln pi_k + ell_k)`` over K rows of :meth:`PopulationPosterior.star_terms`)
+and has no class here; multiple systems (N > 1) are out of scope."""
 from __future__ import annotations
 
 import ctypes as C
@@ -91,6 +97,13 @@ class _Family:
     ranges = ()
 
 
+class _Relation(_Family):
+    """A family whose density depends on the same sample's value of another column of the model, ``on``
+    (:mod:`isochrones_amd.relations`).  ``PopulationModel.pack`` writes the index of that column into ``reserved`` of the
+    family's records."""
+    on = None
+
+
 class PowerLaw(_Family):
     """x^alpha on ``bounds`` = (lo, hi), lo > 0, with ``alpha`` free in the range ``alpha`` (its flat hyper-prior);
     alpha = -1 is normalised by 1 / ln(hi / lo)."""
@@ -156,7 +169,9 @@ class Fixed(_Family):
 
 class PopulationModel:
     """``PopulationModel(mass=PowerLaw((0.1, 10)), feh=TruncatedGaussian((-4, 0.5)))``: one family per value column, at
-    most four; the density of a star's columns is their product."""
+    most four; the density of a star's columns is their product.  A family of :mod:`isochrones_amd.relations`
+    (``feh=LinearGaussian(on="age", ...)``) is conditional on another column of the model; such links may form chains but
+    no cycle."""
 
     def __init__(self, **families):
         if not 1 <= len(families) <= hc.MAX_COLS:
@@ -166,12 +181,36 @@ class PopulationModel:
                 raise TypeError("the family of %r must be a PowerLaw, TruncatedGaussian or Fixed (got %r)" % (col, fam))
         self.columns = tuple(families)
         self.families = tuple(families.values())
+        #: per column the index of the column it is linked to, or -1
+        self.parents = tuple(self._parent(col, fam) for col, fam in families.items())
+        for q, col in enumerate(self.columns):
+            seen, k = {q}, self.parents[q]
+            while k >= 0:
+                if k in seen:
+                    raise ValueError("the links of the population model form a cycle through %r" % (self.columns[k],))
+                seen.add(k)
+                k = self.parents[k]
         self.param_names = tuple("%s.%s" % (c, n) for c, f in families.items() for n in f.names)
         self.ranges = np.array([r for f in self.families for r in f.ranges], dtype=float).reshape(-1, 2)
+
+    def _parent(self, col, fam):
+        if not isinstance(fam, _Relation):
+            return -1
+        if fam.on == col:
+            raise ValueError("the family of %r is linked to its own column" % (col,))
+        if fam.on not in self.columns:
+            raise ValueError("the family of %r is linked to %r, which is no column of the model (%s)"
+                             % (col, fam.on, ", ".join(self.columns)))
+        return self.columns.index(fam.on)
 
     @property
     def n_params(self):
         return len(self.param_names)
+
+    @property
+    def coupled(self):
+        """True if a family is linked to another column: the likelihood then goes through libiso_relation.so."""
+        return any(p >= 0 for p in self.parents)
 
     def pack(self, theta):
         """``theta`` [H, P] -> records [H, Q] (``_hier_cabi.RECORD``), whole columns at a time."""
@@ -183,6 +222,8 @@ class PopulationModel:
         for q, fam in enumerate(self.families):
             col = np.zeros(theta.shape[0], dtype=hc.RECORD)
             fam.fill(col, theta[:, k:k + len(fam.names)])
+            if self.parents[q] >= 0:
+                col["reserved"] = self.parents[q]
             out[:, q] = col
             k += len(fam.names)
         return out
@@ -298,9 +339,21 @@ class PopulationPosterior:
         self.n_unmasked = self.S if mask is None else int(mask.sum())
         self.min_neff_factor = float(min_neff_factor)
         self.injections, self.selection = injections, None
+        if injections is not None and model.coupled:
+            raise ValueError("a coupled population model (%s) takes no injection set yet: the selection library evaluates "
+                             "one-column families only and has no kernel for a linked one" % self._links())
         if injections is not None:
             from .selection import Selection
             self.selection = Selection(injections, model, None if self.host else self.storage.device)
+
+    def _links(self):
+        m = self.model
+        return ", ".join("%s on %s" % (c, m.columns[p]) for c, p in zip(m.columns, m.parents) if p >= 0)
+
+    def _uncoupled(self, what):
+        if self.model.coupled:
+            raise ValueError("%s needs an uncoupled population model: the reweighting library evaluates one-column "
+                             "families only and has no kernel for a linked one (%s)" % (what, self._links()))
 
     # -- evaluation ---------------------------------------------------------------------------------------------------
     def _device_state(self):
@@ -341,11 +394,17 @@ class PopulationPosterior:
         th = np.atleast_2d(th)
         rows = self.model.pack(th)
         H, Q, S = rows.shape[0], rows.shape[1], self.S
-        lib = hc.lib()
+        if self.model.coupled:                  # a linked family: the same call, answered by libiso_relation.so
+            from . import _relation_cabi as rl
+            lib, check = rl.lib(), rl.check
+            fn_host, fn_dev = lib.iso_relation_lnlike_host, lib.iso_relation_lnlike
+        else:
+            lib, check = hc.lib(), hc.check
+            fn_host, fn_dev = lib.iso_hier_lnlike_host, lib.iso_hier_lnlike
         if self.host:
             ell, ess = np.empty((H, S)), np.empty((H, S))
             n_bad, L, mn = np.empty(S, dtype=np.int32), np.empty(H), np.empty(H)
-            interim, mask, drows, fn, stream = self.interim, self.mask, rows, lib.iso_hier_lnlike_host, None
+            interim, mask, drows, fn, stream = self.interim, self.mask, rows, fn_host, None
         else:
             import torch
             device = self.storage.device
@@ -355,14 +414,14 @@ class PopulationPosterior:
             n_bad, L, mn = torch.empty(S, dtype=torch.int32, device=device), torch.empty(H, **f64), torch.empty(H, **f64)
             interim, mask = st["interim"], st["mask"]
             drows = torch.from_numpy(np.ascontiguousarray(rows).view(np.uint8).reshape(-1)).to(device)
-            fn, stream = lib.iso_hier_lnlike, dev.stream_ptr(device.index)
+            fn, stream = fn_dev, dev.stream_ptr(device.index)
         for s0 in range(0, S, self.step):
             n = min(self.step, S - s0)
             last = s0 + n == S
             derived = self._derived(s0, n) if self.derived_cols else None
-            hc.check(fn(self._columns(derived, s0, n), Q, _cabi.CHAIN_PARAM_MAJOR, self.T, S, self.W, s0, n, _ptr(interim),
-                        _ptr(drows), H, _ptr(mask), _ptr(ell), _ptr(ess), _ptr(n_bad), _ptr(L if last else None),
-                        _ptr(mn if last else None), stream))
+            check(fn(self._columns(derived, s0, n), Q, _cabi.CHAIN_PARAM_MAJOR, self.T, S, self.W, s0, n, _ptr(interim),
+                     _ptr(drows), H, _ptr(mask), _ptr(ell), _ptr(ess), _ptr(n_bad), _ptr(L if last else None),
+                     _ptr(mn if last else None), stream))
         out = (L, mn, ell, ess, n_bad)
         if as_tensor and self.host:
             import torch
@@ -433,6 +492,7 @@ class PopulationPosterior:
         sample size of the star's weights) and ``n_bad``.  A masked star is NaN; so are the column summaries of a star with
         no weight left (its ``ess`` is 0)."""
         from . import reweight
+        self._uncoupled("star_posteriors")
         return reweight.star_posteriors(self, theta, columns, q, as_tensors)
 
     def star_weights(self, theta=None, stars=None):
@@ -440,6 +500,7 @@ class PopulationPosterior:
         star, for weighted plots of one's own.  ``stars``: an index, a sequence of indices or a contiguous slice; default:
         all.  On the chain's device (numpy for a host chain)."""
         from . import reweight
+        self._uncoupled("star_weights")
         return reweight.star_weights(self, theta, stars)
 
     def lnprior(self, theta):

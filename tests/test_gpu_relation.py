@@ -1,0 +1,156 @@
+"""iso_relation_lnlike (k_relation_stars, k_relation_total) on the device against iso_relation_lnlike_host and the twin of
+tests/_relation_twin.py, on test_gpu_hier.py's shapes (M = 35, 64 and 1200; H = 1, the row tile, tile + 1 and 3 tiles + 5;
+both layouts) with one link, a chain of links, a parent above its child, parent and child in two storages; the NaN, -inf,
+masked and +-700 cases; slope 0 against iso_hier_lnlike's TRUNCGAUSS.  And bit identity: records of the kinds 1 .. 8 give
+iso_hier_lnlike's bits; a star alone, in a batch and in a sub-range, a row alone and in any tiling, a repeated call and
+another storage and layout give the same bits."""
+import numpy as np
+import pytest
+
+from isochrones_amd import _cabi, _hier_cabi as hc, _relation_cabi as rl
+from tests import _hier_twin as tw, _relation_twin as rt
+
+pytestmark = pytest.mark.gpu
+TILE = rl.ROW_TILE
+PM, RM = _cabi.CHAIN_PARAM_MAJOR, _cabi.CHAIN_ROW_MAJOR
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return rl.lib()
+
+
+@pytest.fixture(scope="module")
+def device():
+    import torch
+    return torch.device("cuda", 0)
+
+
+def _against_host(lib, device, case, what):
+    rc, host = rt.call(lib, case)
+    assert rc == 0, lib.iso_relation_last_error()
+    rc, got = rt.call(lib, case, device=device)
+    assert rc == 0, lib.iso_relation_last_error()
+    want = dict(host, rmax=rt.want(case)["rmax"])
+    rt.assert_matches(host, rt.want(case), what)
+    with np.errstate(invalid="ignore"):
+        d = np.abs(got["ell"] - host["ell"])
+    print(what, "max |d ell| = %.2e" % np.nanmax(np.where(np.isfinite(d), d, 0.0)))
+    rt.assert_matches(got, want, what)
+    rt.assert_matches(got, rt.want(case), what)
+    return got
+
+
+@pytest.mark.parametrize("S, W, T, Q, H, layout, links", rt.SHAPES)
+def test_device_matches_the_host_entry_and_the_twin(lib, device, S, W, T, Q, H, layout, links):
+    case = rt.linked_case(S, W, T, Q, H, seed=7 * Q + H + W, links=links, layout=layout)
+    assert len({w[1] for w in case["where"]}) == 2                  # columns from two storages with different C
+    got = _against_host(lib, device, case, (S, W, T, Q, H, layout, links))
+    assert np.isfinite(got["ell"]).all() and np.isfinite(got["L"]).all()
+
+
+@pytest.mark.parametrize("name", ["parent_nan", "child_out", "mean_60_sigma", "bad_parent", "masked", "span_700"])
+def test_special_cases(lib, device, name):
+    case = rt.special_cases()[name]
+    rt.check_special(name, case, _against_host(lib, device, case, name))
+
+
+def test_a_linked_interim_record_is_nan_on_the_device(lib, device):
+    case = rt.special_cases()["masked"]
+    case = dict(case, interim=case["interim"].copy(), mask=None)
+    case["interim"][1] = case["rows"][0, 1]
+    assert rt.call(lib, case)[0] == rl.ERR_INVALID           # the host entry sees it and refuses
+    rc, got = rt.call(lib, case, device=device)
+    M = case["W"] * case["T"]
+    assert rc == 0 and (got["n_bad"] == M).all() and np.isneginf(got["ell"]).all() and (got["ess"] == 0.0).all()
+
+
+def test_slope_zero_is_the_truncated_gaussian(lib, device):
+    linked, plain = rt.slope_zero_pair()
+    rc, got = rt.call(lib, linked, device=device)
+    rc2, ref = tw.call(hc.lib(), plain, device=device)
+    assert rc == 0 and rc2 == 0
+    lim = 2e-11 * np.maximum(1.0, tw.want(plain)["rmax"] / 100.0)   # each side is within the twin's limit
+    d = np.abs(got["ell"] - ref["ell"])
+    print("slope 0 against TRUNCGAUSS: max |d ell| / limit = %.3f" % np.max(d / lim))
+    assert np.all(d <= lim) and np.array_equal(got["n_bad"], ref["n_bad"])
+    assert np.all(np.abs(got["ess"] - ref["ess"]) <= 2e-10 * ref["ess"])
+
+
+def _same(a, b):
+    return np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
+
+
+@pytest.mark.parametrize("S, W, T, Q, H, layout", [(3, 5, 7, 4, 3 * TILE + 5, RM), (2, 40, 30, 4, 3 * hc.ROW_TILE + 5, PM),
+                                                  (3, 64, 1, 1, TILE + 1, PM)])
+def test_unlinked_records_give_the_bits_of_the_hier_library(lib, device, S, W, T, Q, H, layout):
+    case = tw.random_case(S, W, T, Q, H, seed=7 * Q + H + W, layout=layout)
+    rc, got = rt.call(lib, case, device=device)
+    rc2, ref = tw.call(hc.lib(), case, device=device)
+    assert rc == 0 and rc2 == 0
+    for k in ("ell", "ess", "L", "min_ess", "n_bad"):
+        assert _same(got[k], ref[k]), k
+    assert np.isfinite(got["ell"]).all()
+
+
+@pytest.mark.parametrize("kind", range(1, 9))
+def test_every_unlinked_kind_gives_the_bits_of_the_hier_library(lib, device, kind):
+    case = tw.kind_case(kind)
+    rc, got = rt.call(lib, case, device=device)
+    rc2, ref = tw.call(hc.lib(), case, device=device)
+    assert rc == 0 and rc2 == 0
+    for k in ("ell", "ess", "L", "min_ess", "n_bad"):
+        assert _same(got[k], ref[k]), k
+
+
+@pytest.fixture(scope="module")
+def batch(lib, device):
+    """seven stars, 29 rows, four columns from two storages with a chain of links and a plain column, M = 1200; once"""
+    case = rt.linked_case(7, 40, 30, 4, 3 * TILE + 5, seed=11, links={1: 0, 3: 1})
+    rc, got = rt.call(lib, case, device=device)
+    assert rc == 0, lib.iso_relation_last_error()
+    assert np.isfinite(got["ell"]).all()
+    return case, got
+
+
+def test_a_star_alone_in_a_batch_and_in_a_sub_range(lib, device, batch):
+    case, whole = batch
+    for s in (0, 3, 6):
+        alone = tw.fixed_case(case["x"][:, s:s + 1], list(case["interim"][:, None]),
+                              [[row[q:q + 1] for q in range(len(row))] for row in case["rows"]], 40, 30, seed=50 + s)
+        rc, one = rt.call(lib, alone, device=device)
+        assert rc == 0 and _same(one["ell"][:, 0], whole["ell"][:, s]) and _same(one["ess"][:, 0], whole["ess"][:, s])
+        assert one["n_bad"][0] == whole["n_bad"][s]
+        rc, part = rt.call(lib, case, device=device, ens_begin=s, n_ens_out=1, total=False)
+        assert rc == 0 and _same(part["ell"][:, s], whole["ell"][:, s]) and _same(part["ess"][:, s], whole["ess"][:, s])
+        others = [i for i in range(7) if i != s]
+        assert (part["ell"][:, others] == -7.0).all() and (part["n_bad"][others] == -7).all() and (part["L"] == -7.0).all()
+    rc, part = rt.call(lib, case, device=device, ens_begin=2, n_ens_out=4, total=False)
+    assert rc == 0 and _same(part["ell"][:, 2:6], whole["ell"][:, 2:6]) and _same(part["ess"][:, 2:6], whole["ess"][:, 2:6])
+
+
+def test_a_row_alone_and_in_any_tiling(lib, device, batch):
+    case, whole = batch
+    H = case["rows"].shape[0]
+    for sl in (slice(0, 1), slice(TILE, TILE + 1), slice(H - 1, H), slice(5, 20), slice(3, 3 + TILE), slice(1, H), slice(2, 5)):
+        rc, got = rt.call(lib, case, device=device, rows=case["rows"][sl])
+        assert rc == 0 and _same(got["ell"], whole["ell"][sl]) and _same(got["ess"], whole["ess"][sl]), sl
+        assert _same(got["L"], whole["L"][sl]) and _same(got["min_ess"], whole["min_ess"][sl]), sl
+
+
+def test_repeated_calls_and_another_storage_give_the_same_bits(lib, device, batch):
+    case, whole = batch
+    rc, again = rt.call(lib, case, device=device)
+    assert rc == 0
+    for k in ("L", "min_ess", "ell", "ess", "n_bad"):
+        assert _same(again[k], whole[k]), k
+    # the same columns in one storage of another width, and row-major
+    for layout, split in ((PM, False), (RM, True)):
+        st, where = tw.place(case["x"], 40, 30, layout, seed=99, split=split)
+        assert layout != case["layout"] or [w[1:] for w in where] != [w[1:] for w in case["where"]]
+        moved = dict(case, storages=st, where=where, layout=layout)
+        moved.pop("want", None)
+        rc, got = rt.call(lib, moved, device=device)
+        assert rc == 0
+        for k in ("L", "min_ess", "ell", "ess", "n_bad"):
+            assert _same(got[k], whole[k]), (k, layout)
