@@ -30,5 +30,7 @@ from . import selection
 from .selection import InjectionSet
 from . import relations
 from .relations import LinearGaussian
+from . import binned
+from .binned import Histogram
 
 __version__ = "0.1.0"

@@ -185,6 +185,29 @@ RELATION = KernelLibrary(
     extra_headers=("../../include/isochrones_amd_hier.h", "common/relation_lnf.h", "common/family_lnf.h",
                    "common/chain_view.h", "common/grid_cell.h", "common/last_error.h"))
 
+# HIER's likelihood for a population density that is piecewise constant on a grid of bins over one or two columns
+# (csrc/binned/): a histogram's mean weight is linear in the cell heights, so the chain is compressed once to a table of B
+# numbers per star and every likelihood evaluation is a contraction of that table with the rows' heights.  It reads HIER's
+# records and columns (its header includes isochrones_amd_hier.h) and evaluates the kinds 1 .. 8 through common/family_lnf.h
+# -ffp-contract=off: the compiler fuses nothing, and the sources write no fma(): every product and every sum of the header's
+# definition is rounded on its own (a star's table is bit-identical alone, in any batch, star range and layout, a (row, star)
+# result in any tiling of the hyper rows)
+BINNED = KernelLibrary(
+    name="binned", flags=_NO_CONTRACT,
+    #: every kernel the library compiles (tests/test_binned_library.py pins this set)
+    kernels=("k_binned_compress", "k_binned_rows", "k_binned_total"),
+    #: k_binned_compress compiles to 91 VGPRs, no scratch, 4.4 KB of LDS (a tile's 256 weights and cells, the edges, the
+    #: records) and 5 waves per SIMD.  A lane holds one sample at a time: a column's value, its log and interim term, one
+    #: inlined family evaluation (the FEH one with three exp and a log in flight) and the bracket search; the cell's two sums
+    #: are two registers, since a lane owns one cell.  The column index is a run-time loop, as in k_reweight_weights.  Its 24
+    #: spilled SGPRs (the argument block) go to VGPR lanes, not to scratch.  The kernel runs once per (catalog, edges), so the
+    #: budget is what it compiles to, the 5-waves-per-SIMD one: 96 VGPRs, and no scratch at all.  k_binned_rows (the sums of
+    #: eight rows, 32 registers, and one cell's two loads) is 55 VGPRs at 8 waves with 8.1 KB of LDS (the tile's u and u * u);
+    #: k_binned_total is k_hier_total: 17 VGPRs at 8 waves
+    max_vgpr=96, min_waves=5,
+    extra_headers=("../../include/isochrones_amd_hier.h", "common/family_lnf.h", "common/chain_view.h", "common/grid_cell.h",
+                   "common/last_error.h"))
+
 #: the six libraries the shared builder started with (tests/test_side_libraries_cpu.py pins this tuple to exactly these)
 ALL = (CLUSTER, NESTED, SOLVE, DIAG, DERIVED, PREDICT)
 #: what __graft_entry__.build() and the command line below build, in order: ALL and the libraries added since ALL was
@@ -196,7 +219,7 @@ ADDED = (HIER,)
 #: the libraries added after ADDED was pinned in its turn (tests/test_hier_library.py); __graft_entry__.build() and the
 #: command line below go through BUILD_ORDER + ADDED + NEWER.  The next library goes here: its test asserts membership,
 #: not equality, so this tuple grows
-NEWER = (SELECT, REWEIGHT, RELATION)
+NEWER = (SELECT, REWEIGHT, RELATION, BINNED)
 
 
 if __name__ == "__main__":
