@@ -13,7 +13,8 @@
 //                      every lane: broadcasts.
 //   k_binned_rows      one workgroup per (tile of ROW_TILE rows, block of 256 stars), lane = star: the tile's
 //                      u = exp(lnh - hmx) and u * u in LDS, then per cell one load of A and A2 and eight multiplies and adds.
-//   k_binned_total     one workgroup per row: L and min_ess over the unmasked stars in a fixed order (k_hier_total).
+//   k_binned_total     one workgroup per row: L and min_ess over the unmasked stars in a fixed order (common/hier_block.h, as
+//                      k_hier_total).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -23,28 +24,19 @@
 #include "isochrones_amd_binned.h"
 #include "../common/family_lnf.h"
 #include "../common/chain_view.h"
+#include "../common/hier_columns.h"
+#include "../common/hier_block.h"
 
 namespace {
 
-constexpr int BLOCK = 256;                      // four wavefronts
-constexpr int WAVES = BLOCK / 64;
 constexpr int RT = ISO_BINNED_ROW_TILE;
-constexpr int MAXQ = ISO_HIER_MAX_COLS;
 constexpr int MAXB = ISO_BINNED_MAX_CELLS;
 constexpr int MAXA = ISO_BINNED_MAX_AXES;
 constexpr int MAX_EDGES = MAXB + 1 + 2;         // 64 x 1 bins: 65 + 2 edges
 constexpr int FROZEN = -1;                      // Grid::role: else the axis number
 constexpr int BAD = 1, OUT = 2;                 // sample_term's flag
-static_assert(ISO_HIER_ROW_MAJOR == CHAIN_ROW_MAJOR && ISO_HIER_PARAM_MAJOR == CHAIN_PARAM_MAJOR, "chain layouts");
 static_assert(sizeof(Rec) == 72, "record layout");
 static_assert(MAXB <= 64 && MAXA == 2, "the owners of the cells are the lanes of the first wavefront; two bin terms");
-
-// one column as the kernel reads it: sample (t, w) of ensemble s at base[t * st_t + ((s - first) * W + w) * st_w]
-struct DevCol {
-    const double* base;                         // the storage's first double of the column
-    int64_t st_t, st_w;
-    int32_t first, pad;
-};
 
 // the grid of bins; the same in every lane
 struct Grid {
@@ -76,8 +68,7 @@ __host__ __device__ inline double sample_term(const DevCol* col, const Rec* inte
     int idx = 0, seen = 0;
 #pragma unroll 1
     for (int q = 0; q < G.Q; ++q) {
-        const DevCol& c = col[q];
-        const double x = c.base[(int64_t)t * c.st_t + ((int64_t)(s - c.first) * W + w) * c.st_w];
+        const double x = load(col[q], s, W, t, w);
         const double lx = logs[q] ? log(x) : 0.0;
         const double l0 = lnf(interim[q], x, lx);
         good = good && x == x && l0 == l0 && l0 != neg_inf();
@@ -122,31 +113,6 @@ struct CArgs {
     int32_t* n_out;
     int32_t T, W, n_ens, ens_begin;
 };
-
-// xor butterflies over the 64 lanes, distances 32 .. 1: every lane ends with the same value, in a fixed order
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fmax(v, __shfl_xor(v, d, 64));
-    return v;
-}
-
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fmin(v, __shfl_xor(v, d, 64));
-    return v;
-}
-
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 
 __global__ void __launch_bounds__(BLOCK) k_binned_compress(const CArgs A) {
     __shared__ Rec s_rec[2 * MAXQ];             // [q]: interim; [MAXQ + q]: frozen
@@ -337,30 +303,7 @@ __global__ void __launch_bounds__(BLOCK) k_binned_rows(const RArgs R) {
 __global__ void __launch_bounds__(BLOCK) k_binned_total(const double* __restrict__ ell, const double* __restrict__ ess,
                                                         const int32_t* __restrict__ mask, int n_ens,
                                                         double* __restrict__ L, double* __restrict__ min_ess) {
-    __shared__ double s_red[2 * WAVES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const size_t row = (size_t)blockIdx.x * (size_t)n_ens;
-    double sum = 0.0, mn = HUGE_VAL;
-    for (int s = tid; s < n_ens; s += BLOCK) {
-        if (mask && mask[s] == 0) continue;
-        sum += ell[row + s];
-        mn = fmin(mn, ess[row + s]);
-    }
-    const double a = wave_sum(sum), b = wave_min(mn);
-    if (lane == 0) {
-        s_red[wave] = a;
-        s_red[WAVES + wave] = b;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        L[blockIdx.x] = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
-        min_ess[blockIdx.x] = fmin(fmin(s_red[WAVES], s_red[WAVES + 1]), fmin(s_red[WAVES + 2], s_red[WAVES + 3]));
-    }
-}
-
-DevCol dev_col(const iso_hier_column& c, int layout, int32_t W) {
-    const ChainStrides st = chain_strides(layout, (int64_t)c.n_ens * W, c.ncols);
-    return DevCol{c.base + (int64_t)c.col * st.st_d, st.st_t, st.st_w, c.first, 0};
+    row_total(ell, ess, mask, n_ens, L, min_ess);
 }
 
 // the checks of iso_binned_compress that need no look at device memory; fills G
@@ -383,14 +326,7 @@ int check_compress(const char* who, const iso_hier_column* columns, int32_t Q, i
     else if (n_axes < 1 || n_axes > MAXA) why = "a grid has 1 or 2 binned axes";
     else if (n_frozen < 0 || n_frozen > Q) why = "n_frozen must be 0 to Q";
     else
-        for (int q = 0; q < Q && !why; ++q) {
-            const iso_hier_column& c = columns[q];
-            if (!c.base) why = "null column storage";
-            else if (c.ncols < 1 || c.col < 0 || c.col >= c.ncols) why = "a column index is outside [0, ncols)";
-            else if (c.n_ens < 1 || (int64_t)c.n_ens * W > INT32_MAX) why = "a column storage's n_ens must be at least 1 and n_ens * W below 2^31";
-            else if (c.first < 0 || c.first > ens_begin || (int64_t)ens_begin + n_ens_out > (int64_t)c.first + c.n_ens)
-                why = "a column storage does not hold the ensembles [ens_begin, ens_begin + n_ens_out)";
-        }
+        for (int q = 0; q < Q && !why; ++q) why = column_error(columns[q], W, ens_begin, n_ens_out);
     if (why) return fail(ISO_BINNED_ERR_INVALID, who, why);
     G = Grid{};
     G.Q = Q;
@@ -618,17 +554,7 @@ int iso_binned_lnlike_host(const double* A, const double* A2, const double* mx, 
             ess[(size_t)h * ld + s] = none ? 0.0 : (s1 * s1) / s2;
         }
     }
-    if (L)
-        for (int h = 0; h < H; ++h) {
-            double sum = 0.0, mn = HUGE_VAL;
-            for (int s = 0; s < n_ens; ++s) {
-                if (mask && mask[s] == 0) continue;
-                sum += ell[(size_t)h * ld + s];
-                mn = fmin(mn, ess[(size_t)h * ld + s]);
-            }
-            L[h] = sum;
-            min_ess[h] = mn;
-        }
+    if (L) row_totals_host(ell, ess, mask, n_ens, H, L, min_ess);
     return 0;
 }
 

@@ -1,7 +1,6 @@
-// ln f(x; record) of include/isochrones_amd_hier.h for host and device code: the family arithmetic of an iso_hier_record,
-// restated verbatim from the anonymous namespace of csrc/hier/hier.hip for the libraries that came after it (csrc/select/).
-// hier.hip keeps its own copy until a change that may touch its pinned header list folds it onto this file;
-// tests/test_select_host_abi_cpu.py holds the two bit for bit equal through the *_lnpdf_host entries.
+// ln f(x; record) of include/isochrones_amd_hier.h for host and device code: the family arithmetic of an iso_hier_record.
+// This is its only home: csrc/hier/ and every library on its records (csrc/select/, csrc/reweight/, csrc/relation/,
+// csrc/binned/) compile these lines, kernel and host entry, so a record's term is the same bits in all of them.
 // Internal and of internal linkage.  The source writes no fused multiply-add; it is meant for -ffp-contract=off.
 #ifndef ISO_COMMON_FAMILY_LNF_H
 #define ISO_COMMON_FAMILY_LNF_H
@@ -15,6 +14,7 @@
 
 namespace {
 
+constexpr int MAXQ = ISO_HIER_MAX_COLS;
 constexpr double LN10 = 2.302585092994046;
 
 typedef iso_hier_record Rec;

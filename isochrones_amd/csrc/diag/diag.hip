@@ -20,6 +20,7 @@
 #include "isochrones_amd_diag.h"
 #include "../common/chain_view.h"
 #include "../common/grid_cell.h"
+#include "../common/wave_reduce.h"
 
 namespace {
 
@@ -44,13 +45,6 @@ struct Shape {
 // means and first values, the tile
 size_t lds_doubles(int W, int K, int WT, int Tp) {
     return (size_t)GROUPS * (K + 1) + 4 * (size_t)W + 2 * (size_t)WT + (size_t)WT * Tp;
-}
-
-// xor butterfly over the 64 lanes, distances 32 .. 1: every lane ends with the same sum, in a fixed order
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
 }
 
 // the lag sums of one item over the walkers of group g in the tile; NJ = how many of the lane's lags are <= K in any lane

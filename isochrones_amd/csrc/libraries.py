@@ -60,6 +60,16 @@ SOLVE = KernelLibrary(
 _CHAIN_HEADERS = ("common/grid_cell.h", "common/chain_view.h", "common/last_error.h")
 #: the same for the two that interpolate grid cells along it (grid_interp.h: the cell the population library shares)
 _CELL_HEADERS = _CHAIN_HEADERS + ("common/grid_interp.h",)
+#: shared by HIER and the four libraries on its records: the family arithmetic (family_lnf.h, its only home) and the
+#: wavefront reductions.  Every spec names every header its sources reach, directly or through another header: one that is
+#: not named is not in the source digest (tests/test_side_libraries_cpu.py follows the #include lines)
+_HIER_HEADERS = ("common/family_lnf.h", "common/grid_cell.h", "common/last_error.h", "common/wave_reduce.h")
+#: the same for the four that are not HIER, whose own header isochrones_amd_hier.h is
+_RECORD_HEADERS = ("../../include/isochrones_amd_hier.h",) + _HIER_HEADERS
+#: an iso_hier_column as the kernels read it (hier_columns.h), for the libraries that read stored chains through one
+_COLUMN_HEADERS = ("common/hier_columns.h", "common/chain_view.h")
+#: the entry points HIER and RELATION share (hier_lnlike.h) and the row total they share with BINNED (hier_block.h)
+_LNLIKE_HEADERS = _COLUMN_HEADERS + ("common/hier_block.h", "common/hier_lnlike.h")
 
 # per-star chain convergence diagnostics (csrc/diag/)
 # -ffp-contract=off: the compiler fuses nothing on its own; the kernel's fused multiply-adds are the ones written as fma(),
@@ -70,7 +80,7 @@ DIAG = KernelLibrary(
     kernels=("k_diag_chain",),
     #: k_diag_chain compiles to 44 VGPRs, no scratch and 8 waves per SIMD.  Its inner loop is two LDS reads per multiply-add,
     #: hidden by the other wavefronts of the CU, so the budget is the 8-waves-per-SIMD one: 64 VGPRs, and no scratch at all
-    max_vgpr=64, min_waves=8, extra_headers=_CHAIN_HEADERS)
+    max_vgpr=64, min_waves=8, extra_headers=_CHAIN_HEADERS + ("common/wave_reduce.h",))
 
 # model-grid columns along a stored chain (csrc/derived/)
 # -ffp-contract=off: the compiler fuses nothing, and the sources write no fma(): every product and every sum of the header's
@@ -125,11 +135,11 @@ HIER = KernelLibrary(
     #: inlined family evaluations, the FEH one with three exp and a log in flight.  Held to 4 waves (128 VGPRs) it spills 45
     #: registers to scratch; the per-(row, sample) exp binds, not latency, so the budget is the 3-waves-per-SIMD one: 168
     #: VGPRs, and no scratch at all.  k_hier_total is 17 VGPRs at 8 waves
-    max_vgpr=168, min_waves=3, extra_headers=_CHAIN_HEADERS)
+    max_vgpr=168, min_waves=3, extra_headers=_HIER_HEADERS + _LNLIKE_HEADERS)
 
 # the detectable fraction of a population density from an injection set (csrc/select/): the selection term of HIER's
 # likelihood.  It reads HIER's records (its header includes isochrones_amd_hier.h) and evaluates them through
-# common/family_lnf.h, the family arithmetic of hier.hip restated for the libraries after it
+# common/family_lnf.h, the family arithmetic HIER itself compiles
 # -ffp-contract=off: the compiler fuses nothing, and the sources write no fma(): every product and every sum of the header's
 # definition is rounded on its own (a row is bit-identical alone, in any tiling of the hyper rows and on every call)
 SELECT = KernelLibrary(
@@ -140,8 +150,7 @@ SELECT = KernelLibrary(
     #: scratch, 3.1 KB of LDS and 3 waves per SIMD, for the same reason (the accumulators of eight rows, eight inlined
     #: family evaluations); the budget is the 3-waves-per-SIMD one: 168 VGPRs, and no scratch at all.  k_select_total is
     #: 44 VGPRs at 8 waves
-    max_vgpr=168, min_waves=3,
-    extra_headers=("../../include/isochrones_amd_hier.h", "common/family_lnf.h", "common/grid_cell.h", "common/last_error.h"))
+    max_vgpr=168, min_waves=3, extra_headers=_RECORD_HEADERS)
 
 # the population-informed posterior of every star from its stored chain (csrc/reweight/): per-sample weights under the hyper
 # rows of a fitted population, and weighted per-star summaries.  It reads HIER's records and columns (its header includes
@@ -160,9 +169,7 @@ REWEIGHT = KernelLibrary(
     #: go to VGPR lanes, not to scratch.  Held to 5 waves (96 VGPRs) it spills 2 registers to scratch; the per-(row, sample)
     #: exp binds, not latency, so the budget is the 4-waves-per-SIMD one: 128 VGPRs, and no scratch at all.
     #: k_reweight_summary (16 bins of a radix pass in registers) is 59 VGPRs at 8 waves
-    max_vgpr=128, min_waves=4,
-    extra_headers=("../../include/isochrones_amd_hier.h", "common/family_lnf.h", "common/chain_view.h", "common/grid_cell.h",
-                   "common/last_error.h"))
+    max_vgpr=128, min_waves=4, extra_headers=_RECORD_HEADERS + _COLUMN_HEADERS)
 
 # HIER's likelihood for a population density that links columns (csrc/relation/): a column's Gaussian follows another column
 # linearly, so its truncation normaliser is per (hyper row, sample) and is evaluated in the kernel.  It reads HIER's records
@@ -181,9 +188,7 @@ RELATION = KernelLibrary(
     #: against 68.3 ms): the per-sample work is shared by half as many rows.  So the budget is the
     #: 2-waves-per-SIMD one: 256 VGPRs, and no scratch at all.  Its 43 spilled SGPRs (the argument block) go to VGPR lanes, not
     #: to scratch.  k_relation_total is k_hier_total: 17 VGPRs at 8 waves
-    max_vgpr=256, min_waves=2,
-    extra_headers=("../../include/isochrones_amd_hier.h", "common/relation_lnf.h", "common/family_lnf.h",
-                   "common/chain_view.h", "common/grid_cell.h", "common/last_error.h"))
+    max_vgpr=256, min_waves=2, extra_headers=_RECORD_HEADERS + ("common/relation_lnf.h",) + _LNLIKE_HEADERS)
 
 # HIER's likelihood for a population density that is piecewise constant on a grid of bins over one or two columns
 # (csrc/binned/): a histogram's mean weight is linear in the cell heights, so the chain is compressed once to a table of B
@@ -204,9 +209,7 @@ BINNED = KernelLibrary(
     #: budget is what it compiles to, the 5-waves-per-SIMD one: 96 VGPRs, and no scratch at all.  k_binned_rows (the sums of
     #: eight rows, 32 registers, and one cell's two loads) is 55 VGPRs at 8 waves with 8.1 KB of LDS (the tile's u and u * u);
     #: k_binned_total is k_hier_total: 17 VGPRs at 8 waves
-    max_vgpr=96, min_waves=5,
-    extra_headers=("../../include/isochrones_amd_hier.h", "common/family_lnf.h", "common/chain_view.h", "common/grid_cell.h",
-                   "common/last_error.h"))
+    max_vgpr=96, min_waves=5, extra_headers=_RECORD_HEADERS + _COLUMN_HEADERS + ("common/hier_block.h",))
 
 #: the six libraries the shared builder started with (tests/test_side_libraries_cpu.py pins this tuple to exactly these)
 ALL = (CLUSTER, NESTED, SOLVE, DIAG, DERIVED, PREDICT)

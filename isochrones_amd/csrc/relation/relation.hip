@@ -3,7 +3,8 @@
 // importance weight and its effective sample size; per row their total.  See include/isochrones_amd_relation.h for the
 // linked kind, include/isochrones_amd_hier.h for everything else, DESIGN.md section 20 for the mapping and the resources.
 //
-// Two kernels, 256-thread workgroups (four wavefronts), float64, on the plan of csrc/hier/hier.hip:
+// Two kernels, 256-thread workgroups (four wavefronts), float64, on the plan of csrc/hier/hier.hip and launched through the
+// entry points it shares with it (common/hier_lnlike.h: the checks, the argument block, the host reference):
 //   k_relation_stars  one workgroup per (star, tile of ROW_TILE hyper rows).  The interim records, the tile's records and
 //                     the column descriptors are staged in LDS, and next to them per (row, column) of the tile whether the
 //                     record is linked and to which parent.  A lane loads all Q values of its sample first (a linked term
@@ -13,70 +14,23 @@
 //                     loop as it is; in a linked one the two erfc and the log of the per-sample normaliser run only for the
 //                     linked rows, under a scalar branch, and the parent's value comes from a chain of selects on a scalar,
 //                     not from a dynamic register index.
-//   k_relation_total  one workgroup per row: L and min_ess over the unmasked stars in a fixed order (k_hier_total).
+//   k_relation_total  one workgroup per row: L and min_ess over the unmasked stars in a fixed order (common/hier_block.h, as
+//                     k_hier_total).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
-#include <vector>
-
 #include "isochrones_amd_relation.h"
 #include "../common/relation_lnf.h"
-#include "../common/chain_view.h"
+#include "../common/hier_lnlike.h"
 
 namespace {
 
-constexpr int BLOCK = 256;                      // four wavefronts
-constexpr int WAVES = BLOCK / 64;
 constexpr int RT = ISO_RELATION_ROW_TILE;
-constexpr int MAXQ = ISO_HIER_MAX_COLS;
+constexpr LnlikeLib LIB{ISO_RELATION_ERR_INVALID, ISO_RELATION_ERR_HIP, RT};
 constexpr int NOT_LINKED = -1, BAD_PARENT = -2; // s_par: else the parent column
-static_assert(ISO_HIER_ROW_MAJOR == CHAIN_ROW_MAJOR && ISO_HIER_PARAM_MAJOR == CHAIN_PARAM_MAJOR, "chain layouts");
 static_assert(sizeof(Rec) == 72, "record layout");
 static_assert(MAXQ == 4 && RT * MAXQ <= BLOCK, "the select chains and the staging below are written for four columns");
-
-// one column as the kernel reads it: sample (t, w) of ensemble s at base[t * st_t + ((s - first) * W + w) * st_w]
-struct DevCol {
-    const double* base;                         // the storage's first double of the column
-    int64_t st_t, st_w;
-    int32_t first, pad;
-};
-
-struct Args {
-    DevCol col[MAXQ];
-    const Rec* interim;
-    const Rec* rows;
-    const int32_t* mask;
-    double* ell;
-    double* ess;
-    int32_t* n_bad;
-    int32_t Q, T, W, H, n_ens, ens_begin, ntiles, pad;
-};
-
-// xor butterflies over the 64 lanes, distances 32 .. 1: every lane ends with the same value, in a fixed order
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fmax(v, __shfl_xor(v, d, 64));
-    return v;
-}
-
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fmin(v, __shfl_xor(v, d, 64));
-    return v;
-}
-
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 
 // the sample's value of column k, for a k that is the same in every lane
 __device__ __forceinline__ double pick(double x0, double x1, double x2, double x3, int k) {
@@ -85,10 +39,6 @@ __device__ __forceinline__ double pick(double x0, double x1, double x2, double x
     v = (k == 2) ? x2 : v;
     v = (k == 3) ? x3 : v;
     return v;
-}
-
-__device__ __forceinline__ double load(const DevCol& c, int s, int W, int t, int w) {
-    return c.base[(int64_t)t * c.st_t + ((int64_t)(s - c.first) * W + w) * c.st_w];
 }
 
 __global__ void __launch_bounds__(BLOCK) k_relation_stars(const Args A) {
@@ -270,56 +220,7 @@ __global__ void __launch_bounds__(BLOCK) k_relation_stars(const Args A) {
 __global__ void __launch_bounds__(BLOCK) k_relation_total(const double* __restrict__ ell, const double* __restrict__ ess,
                                                           const int32_t* __restrict__ mask, int n_ens,
                                                           double* __restrict__ L, double* __restrict__ min_ess) {
-    __shared__ double s_red[2 * WAVES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const size_t row = (size_t)blockIdx.x * (size_t)n_ens;
-    double sum = 0.0, mn = HUGE_VAL;
-    for (int s = tid; s < n_ens; s += BLOCK) {
-        if (mask && mask[s] == 0) continue;
-        sum += ell[row + s];
-        mn = fmin(mn, ess[row + s]);
-    }
-    const double a = wave_sum(sum), b = wave_min(mn);
-    if (lane == 0) {
-        s_red[wave] = a;
-        s_red[WAVES + wave] = b;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        L[blockIdx.x] = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
-        min_ess[blockIdx.x] = fmin(fmin(s_red[WAVES], s_red[WAVES + 1]), fmin(s_red[WAVES + 2], s_red[WAVES + 3]));
-    }
-}
-
-int check_args(const char* who, const iso_hier_column* columns, int32_t Q, int layout, int64_t nsteps, int32_t n_ens,
-               int32_t W, int32_t ens_begin, int32_t n_ens_out, const Rec* interim, const Rec* rows, int32_t H,
-               const double* ell, const double* ess, const int32_t* n_bad, const double* L, const double* min_ess) {
-    ChainShape s{layout, nsteps, n_ens, W, 1};
-    s.ens_begin = ens_begin;
-    s.n_ens_out = n_ens_out;
-    const char* why = nullptr;
-    if (!columns || !interim || !rows || !ell || !ess || !n_bad) why = "null pointer";
-    else if ((L == nullptr) != (min_ess == nullptr)) why = "L and min_ess go together (both or neither)";
-    else if (Q < 1 || Q > MAXQ) why = "Q must be 1 to 4 columns";
-    else if (H < 1) why = "H must be at least 1";
-    else if ((why = chain_shape_error(CHAIN_CHECK_LAYOUT | CHAIN_CHECK_SIZES | CHAIN_CHECK_RANGE | CHAIN_CHECK_ROWS, s))) {}
-    else if (nsteps * (int64_t)W > INT32_MAX) why = "more than 2^31 - 1 samples per star (thin the chain)";
-    else if ((int64_t)n_ens_out * ((H + RT - 1) / RT) > INT32_MAX) why = "more than 2^31 - 1 (star, row tile) pairs (split the call)";
-    else
-        for (int q = 0; q < Q && !why; ++q) {
-            const iso_hier_column& c = columns[q];
-            if (!c.base) why = "null column storage";
-            else if (c.ncols < 1 || c.col < 0 || c.col >= c.ncols) why = "a column index is outside [0, ncols)";
-            else if (c.n_ens < 1 || (int64_t)c.n_ens * W > INT32_MAX) why = "a column storage's n_ens must be at least 1 and n_ens * W below 2^31";
-            else if (c.first < 0 || c.first > ens_begin || (int64_t)ens_begin + n_ens_out > (int64_t)c.first + c.n_ens)
-                why = "a column storage does not hold the ensembles [ens_begin, ens_begin + n_ens_out)";
-        }
-    return why ? fail(ISO_RELATION_ERR_INVALID, who, why) : 0;
-}
-
-DevCol dev_col(const iso_hier_column& c, int layout, int32_t W) {
-    const ChainStrides st = chain_strides(layout, (int64_t)c.n_ens * W, c.ncols);
-    return DevCol{c.base + (int64_t)c.col * st.st_d, st.st_t, st.st_w, c.first, 0};
+    row_total(ell, ess, mask, n_ens, L, min_ess);
 }
 
 }  // namespace
@@ -334,120 +235,24 @@ int iso_relation_lnlike(const iso_hier_column* columns, int32_t Q, int layout, i
                         int32_t ens_begin, int32_t n_ens_out, const iso_hier_record* interim, const iso_hier_record* rows,
                         int32_t H, const int32_t* mask, double* ell, double* ess, int32_t* n_bad, double* L,
                         double* min_ess, void* stream) {
-    g_err[0] = 0;
-    const int rc = check_args("iso_relation_lnlike", columns, Q, layout, nsteps, n_ens, W, ens_begin, n_ens_out, interim,
-                              rows, H, ell, ess, n_bad, L, min_ess);
-    if (rc) return rc;
-    Args A;
-    for (int q = 0; q < MAXQ; ++q) A.col[q] = dev_col(columns[q < Q ? q : 0], layout, W);
-    A.interim = interim;
-    A.rows = rows;
-    A.mask = mask;
-    A.ell = ell;
-    A.ess = ess;
-    A.n_bad = n_bad;
-    A.Q = Q;
-    A.T = (int32_t)nsteps;
-    A.W = W;
-    A.H = H;
-    A.n_ens = n_ens;
-    A.ens_begin = ens_begin;
-    A.ntiles = (H + RT - 1) / RT;
-    A.pad = 0;
-    hipLaunchKernelGGL(k_relation_stars, dim3((unsigned)n_ens_out * (unsigned)A.ntiles), dim3(BLOCK), 0, (hipStream_t)stream, A);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(ISO_RELATION_ERR_HIP, hipGetErrorString(e));
-    if (L) {
-        hipLaunchKernelGGL(k_relation_total, dim3((unsigned)H), dim3(BLOCK), 0, (hipStream_t)stream, (const double*)ell,
-                           (const double*)ess, mask, (int)n_ens, L, min_ess);
-        e = hipGetLastError();
-        if (e != hipSuccess) return fail(ISO_RELATION_ERR_HIP, hipGetErrorString(e));
-    }
-    return 0;
+    return lnlike_launch("iso_relation_lnlike", LIB, k_relation_stars, k_relation_total,
+                         LnlikeCall{columns, Q, layout, nsteps, n_ens, W, ens_begin, n_ens_out, interim, rows, H, mask, ell,
+                                    ess, n_bad, L, min_ess, stream});
 }
 
 int iso_relation_lnlike_host(const iso_hier_column* columns, int32_t Q, int layout, int64_t nsteps, int32_t n_ens, int32_t W,
                              int32_t ens_begin, int32_t n_ens_out, const iso_hier_record* interim,
                              const iso_hier_record* rows, int32_t H, const int32_t* mask, double* ell, double* ess,
                              int32_t* n_bad, double* L, double* min_ess, void* stream) {
-    (void)stream;
-    g_err[0] = 0;
     const char* who = "iso_relation_lnlike_host";
-    const int rc = check_args(who, columns, Q, layout, nsteps, n_ens, W, ens_begin, n_ens_out, interim, rows, H, ell, ess,
-                              n_bad, L, min_ess);
+    const LnlikeCall c{columns, Q, layout, nsteps, n_ens, W, ens_begin, n_ens_out, interim, rows, H, mask, ell, ess, n_bad,
+                       L, min_ess, stream};
+    const int rc = lnlike_check(who, LIB, c);
     if (rc) return rc;
     for (int q = 0; q < Q; ++q)
         if (interim[q].kind == ISO_RELATION_LINGAUSS)
             return fail(ISO_RELATION_ERR_INVALID, who, "an interim record is linked (interim records are of the kinds 1 to 8)");
-    DevCol col[MAXQ];
-    for (int q = 0; q < Q; ++q) col[q] = dev_col(columns[q], layout, W);
-    const int T = (int)nsteps, M = T * W;
-    const size_t ld = (size_t)n_ens;
-    std::vector<double> x((size_t)Q * M), lx((size_t)Q * M), l0((size_t)Q * M), r(M);
-    std::vector<char> good(M);
-    for (int s = ens_begin; s < ens_begin + n_ens_out; ++s) {
-        if (mask && mask[s] == 0) {
-            for (int h = 0; h < H; ++h) ell[(size_t)h * ld + s] = ess[(size_t)h * ld + s] = qnan();
-            n_bad[s] = 0;
-            continue;
-        }
-        int nb = 0;
-        for (int m = 0; m < M; ++m) {
-            bool g = true;
-            const int t = m / W, w = m - t * W;
-            for (int q = 0; q < Q; ++q) {
-                const DevCol& c = col[q];
-                const double v = c.base[(int64_t)t * c.st_t + ((int64_t)(s - c.first) * W + w) * c.st_w];
-                const size_t i = (size_t)q * M + m;
-                x[i] = v;
-                lx[i] = log(v);
-                l0[i] = lnf(interim[q], v, lx[i]);
-                g = g && v == v && l0[i] == l0[i] && l0[i] != neg_inf();
-            }
-            good[m] = g;
-            nb += g ? 0 : 1;
-        }
-        n_bad[s] = nb;
-        for (int h = 0; h < H; ++h) {
-            double mx = neg_inf();
-            for (int m = 0; m < M; ++m) {
-                double xs[MAXQ] = {0.0, 0.0, 0.0, 0.0};
-                for (int q = 0; q < Q; ++q) xs[q] = x[(size_t)q * M + m];
-                double acc = 0.0;
-                for (int q = 0; q < Q; ++q) {
-                    const size_t i = (size_t)q * M + m;
-                    double lf = relation_lnf(rows[(size_t)h * Q + q], x[i], lx[i], xs, q, Q);
-                    lf = (lf == lf) ? lf : neg_inf();
-                    const double d = lf - l0[i];
-                    acc = (q == 0) ? d : acc + d;
-                }
-                r[m] = acc;
-                if (good[m]) mx = fmax(mx, acc);
-            }
-            const double sub = (mx == neg_inf()) ? 0.0 : mx;
-            double S1 = 0.0, S2 = 0.0;
-            for (int m = 0; m < M; ++m) {
-                const double wgt = good[m] ? exp(r[m] - sub) : 0.0;
-                S1 += wgt;
-                S2 += wgt * wgt;
-            }
-            const bool none = !(S1 > 0.0);
-            ell[(size_t)h * ld + s] = none ? neg_inf() : (sub + log(S1)) - log((double)M);
-            ess[(size_t)h * ld + s] = none ? 0.0 : (S1 * S1) / S2;
-        }
-    }
-    if (L)
-        for (int h = 0; h < H; ++h) {
-            double sum = 0.0, mn = HUGE_VAL;
-            for (int s = 0; s < n_ens; ++s) {
-                if (mask && mask[s] == 0) continue;
-                sum += ell[(size_t)h * ld + s];
-                mn = fmin(mn, ess[(size_t)h * ld + s]);
-            }
-            L[h] = sum;
-            min_ess[h] = mn;
-        }
-    return 0;
+    return lnlike_host(c, relation_lnf);
 }
 
 int iso_relation_lnpdf_host(const iso_hier_record* records, int32_t n_rec, const double* x, const double* xp, int64_t n,

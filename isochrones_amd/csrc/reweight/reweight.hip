@@ -24,26 +24,19 @@
 #include "isochrones_amd_reweight.h"
 #include "../common/family_lnf.h"
 #include "../common/chain_view.h"
+#include "../common/hier_columns.h"
+#include "../common/wave_reduce.h"
 
 namespace {
 
 constexpr int BLOCK = 256;                      // four wavefronts
 constexpr int WAVES = BLOCK / 64;
 constexpr int TILE = ISO_REWEIGHT_ROW_TILE;
-constexpr int MAXQ = ISO_HIER_MAX_COLS;
 constexpr int MAXV = ISO_REWEIGHT_MAX_VALUES;
 constexpr int MAXK = ISO_REWEIGHT_MAX_PROBS;
 constexpr int NBIN = 16, DIGIT_BITS = 4, NPASS = 64 / DIGIT_BITS;
 constexpr uint64_t SIGN = 0x8000000000000000ULL;
-static_assert(ISO_HIER_ROW_MAJOR == CHAIN_ROW_MAJOR && ISO_HIER_PARAM_MAJOR == CHAIN_PARAM_MAJOR, "chain layouts");
 static_assert(sizeof(Rec) == 72, "record layout");
-
-// one column as the kernels read it: sample (t, w) of ensemble s at base[t * st_t + ((s - first) * W + w) * st_w]
-struct DevCol {
-    const double* base;                         // the storage's first double of the column
-    int64_t st_t, st_w;
-    int32_t first, pad;
-};
 
 struct WArgs {
     DevCol col[MAXQ];
@@ -81,19 +74,6 @@ __host__ __device__ inline double value_of(uint64_t key) {
     union { double d; uint64_t u; } x;
     x.u = (key & SIGN) ? (key ^ SIGN) : ~key;
     return x.d;
-}
-
-// xor butterflies over the 64 lanes, distances 32 .. 1: every lane ends with the same value, in a fixed order
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
 }
 
 __global__ void __launch_bounds__(BLOCK) k_reweight_weights(const WArgs A) {
@@ -164,8 +144,7 @@ __global__ void __launch_bounds__(BLOCK) k_reweight_weights(const WArgs A) {
             bool good = true;
 #pragma unroll 1
             for (int q = 0; q < Q; ++q) {
-                const DevCol c = s_col[q];
-                const double xv = c.base[(int64_t)t * c.st_t + ((int64_t)(s - c.first) * W + w) * c.st_w];
+                const double xv = load(s_col[q], s, W, t, w);
                 const double lv = s_log[q] ? log(xv) : 0.0;         // workgroup-uniform choice
                 const double l = lnf(s_rec[q], xv, lv);
                 good = good && xv == xv && l == l && l != neg_inf();
@@ -364,15 +343,6 @@ __global__ void __launch_bounds__(BLOCK) k_reweight_summary(const SArgs A) {
     }
 }
 
-const char* column_error(const iso_hier_column& c, int32_t W, int32_t ens_begin, int32_t n_ens_out) {
-    if (!c.base) return "null column storage";
-    if (c.ncols < 1 || c.col < 0 || c.col >= c.ncols) return "a column index is outside [0, ncols)";
-    if (c.n_ens < 1 || (int64_t)c.n_ens * W > INT32_MAX) return "a column storage's n_ens must be at least 1 and n_ens * W below 2^31";
-    if (c.first < 0 || c.first > ens_begin || (int64_t)ens_begin + n_ens_out > (int64_t)c.first + c.n_ens)
-        return "a column storage does not hold the ensembles [ens_begin, ens_begin + n_ens_out)";
-    return nullptr;
-}
-
 int check_args(const char* who, const iso_hier_column* columns, int32_t Q, const iso_hier_column* values, int32_t V,
                int layout, int64_t nsteps, int32_t n_ens, int32_t W, int32_t ens_begin, int32_t n_ens_out, const Rec* interim,
                const Rec* rows, int32_t H, const double* ln_norm, const double* probs, int32_t K, const double* weights,
@@ -399,11 +369,6 @@ int check_args(const char* who, const iso_hier_column* columns, int32_t Q, const
         for (int v = 0; v < V && !why; ++v) why = column_error(values[v], W, ens_begin, n_ens_out);
     }
     return why ? fail(ISO_REWEIGHT_ERR_INVALID, who, why) : 0;
-}
-
-DevCol dev_col(const iso_hier_column& c, int layout, int32_t W) {
-    const ChainStrides st = chain_strides(layout, (int64_t)c.n_ens * W, c.ncols);
-    return DevCol{c.base + (int64_t)c.col * st.st_d, st.st_t, st.st_w, c.first, 0};
 }
 
 }  // namespace
@@ -501,8 +466,7 @@ int iso_reweight_stars_host(const iso_hier_column* columns, int32_t Q, const iso
             double x[MAXQ], lx[MAXQ], l0[MAXQ];
             bool good = true;
             for (int q = 0; q < Q; ++q) {
-                const DevCol& c = col[q];
-                x[q] = c.base[(int64_t)t * c.st_t + ((int64_t)(s - c.first) * W + w) * c.st_w];
+                x[q] = load(col[q], s, W, t, w);
                 lx[q] = log(x[q]);
                 l0[q] = lnf(interim[q], x[q], lx[q]);
                 good = good && x[q] == x[q] && l0[q] == l0[q] && l0[q] != neg_inf();
@@ -535,7 +499,7 @@ int iso_reweight_stars_host(const iso_hier_column* columns, int32_t Q, const iso
             int nn = 0;
             for (int m = 0; m < M; ++m) {
                 const int t = m / W, w = m - t * W;
-                const double y0 = c.base[(int64_t)t * c.st_t + ((int64_t)(s - c.first) * W + w) * c.st_w];
+                const double y0 = load(c, s, W, t, w);
                 const bool isn = y0 != y0;
                 nn += isn ? 1 : 0;
                 y[m] = isn ? 0.0 : y0 + 0.0;

@@ -22,13 +22,13 @@
 #include "isochrones_amd_select.h"
 #include "../common/family_lnf.h"
 #include "../common/last_error.h"
+#include "../common/wave_reduce.h"
 
 namespace {
 
 constexpr int BLOCK = 256;                      // four wavefronts
 constexpr int WAVES = BLOCK / 64;
 constexpr int RT = ISO_HIER_ROW_TILE;
-constexpr int MAXQ = ISO_HIER_MAX_COLS;
 constexpr int CHUNK = ISO_SELECT_CHUNK;
 static_assert(sizeof(Rec) == 72, "record layout");
 static_assert(CHUNK % BLOCK == 0, "a chunk is whole passes of the workgroup");
@@ -45,25 +45,6 @@ struct Args {
 };
 
 __host__ __device__ inline int64_t n_chunks(int64_t J) { return (J + CHUNK - 1) / CHUNK; }
-
-// xor butterflies over the 64 lanes, distances 32 .. 1: every lane ends with the same value, in a fixed order
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fmax(v, __shfl_xor(v, d, 64));
-    return v;
-}
-
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 
 __global__ void __launch_bounds__(BLOCK) k_select_partial(const Args A) {
     __shared__ Rec s_rec[(RT + 1) * MAXQ];      // [0][q]: draw; [1 + k][q]: row k of the tile

@@ -25,9 +25,12 @@ def _built():
 def test_builds_for_gfx950():
     assert "--offload-arch=gfx950" in B.FLAGS and "-ffp-contract=off" in B.FLAGS and "-fno-fast-math" in B.FLAGS
     assert os.path.basename(_built()) == "libiso_hier.so"
+    for path in B.sources() + [h for h in B.headers() if os.path.basename(os.path.dirname(h)) == "common"]:
+        src = open(path).read()
+        assert not re.search(r"\bfma\s*\(", src), path          # the header's arithmetic has no fused multiply-add
+        assert not re.search(r"atomic", src), path              # L is summed in a fixed order
     src = open(os.path.join(B.SRC, "hier.hip")).read()
-    assert not re.search(r"\bfma\s*\(", src)                    # the header's arithmetic has no fused multiply-add
-    assert not re.search(r"atomic", src)                        # L is summed in a fixed order
+    assert '#include "../common/family_lnf.h"' in src and "feh_shape" not in src     # the family arithmetic is the shared one
 
 
 def test_exports_exactly_the_bound_symbols():
@@ -92,7 +95,9 @@ def test_build_lists():
     assert len({s.source_digest() for s in every}) == len(every)
     assert not any("hier" in os.path.basename(s) for s in main.sources())
     assert os.path.exists(B.HEADER) and B.HEADER in B.headers()
-    assert [os.path.basename(h) for h in B.headers()] == ["isochrones_amd_hier.h", "grid_cell.h", "chain_view.h", "last_error.h"]
+    assert [os.path.basename(h) for h in B.headers()] == [
+        "isochrones_amd_hier.h", "family_lnf.h", "grid_cell.h", "last_error.h", "wave_reduce.h", "hier_columns.h", "chain_view.h",
+        "hier_block.h", "hier_lnlike.h"]
     # what build() iterates, and what git ignores
     entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
     assert "libraries.BUILD_ORDER + libraries.ADDED" in entry

@@ -4,6 +4,7 @@ spec's digest follows what it is built from and nothing else, the gates report e
 import dataclasses
 import itertools
 import os
+import re
 import shutil
 import types
 
@@ -66,6 +67,51 @@ def test_nested_digest_covers_the_main_library_headers_it_includes():
     with pytest.raises(OSError):
         gone.source_digest()
     assert dataclasses.replace(SOLVE, extra_headers=SOLVE.extra_headers + ("no_such_dir/*.h",)).headers() == SOLVE.headers()
+
+
+def _reached_headers(spec):
+    """Every file a quoted #include of the spec's sources reaches: looked up next to the including file, then in include/
+    (the -I of every spec), and followed on through the library's own directory, csrc/common/ and include/."""
+    followed = {os.path.realpath(d) for d in (spec.SRC, os.path.join(sidelib.HERE, "common"), sidelib.INCLUDE)}
+    seen, todo = set(), list(spec.sources())
+    while todo:
+        path = todo.pop()
+        for name in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), re.M):
+            hits = [p for p in (os.path.join(os.path.dirname(path), name), os.path.join(sidelib.INCLUDE, name)) if os.path.exists(p)]
+            assert hits, (path, name)
+            hit = os.path.realpath(hits[0])
+            if hit not in seen:
+                seen.add(hit)
+                if os.path.dirname(hit) in followed:
+                    todo.append(hit)
+    return seen
+
+
+@pytest.mark.parametrize("spec", libraries.BUILD_ORDER + libraries.ADDED + libraries.NEWER, ids=lambda s: s.name)
+def test_the_digest_covers_every_header_the_sources_reach(spec):
+    """A header that is reached but not listed would not rebuild the library when it is edited."""
+    listed = {os.path.realpath(h) for h in spec.headers()}
+    missing = sorted(os.path.relpath(h, sidelib.HERE) for h in _reached_headers(spec) - listed)
+    assert not missing, (spec.name, missing)
+    if spec in (libraries.HIER,) + libraries.NEWER:
+        assert any(h.endswith("family_lnf.h") for h in listed) and any(h.endswith("wave_reduce.h") for h in listed)
+
+
+def test_the_population_libraries_keep_no_copies_of_what_they_share():
+    """hier, select, reweight, relation and binned: the family arithmetic, the wavefront reductions and the column view live in
+    csrc/common/ alone, and the three row-total kernels are one body."""
+    for spec in (libraries.HIER,) + libraries.NEWER:
+        (path,) = spec.sources()
+        src = open(path).read()
+        for gone in ("__shfl_xor", "struct DevCol", "feh_shape"):
+            assert gone not in src, (spec.name, gone)
+    assert [s.name for s in (libraries.HIER,) + libraries.NEWER] == ["hier", "select", "reweight", "relation", "binned"]
+    for name in ("hier", "relation", "binned"):
+        src = open(os.path.join(sidelib.HERE, name, name + ".hip")).read()
+        (body,) = re.findall(r"__global__[^{;]*\bk_%s_total\s*\([^)]*\)\s*\{(.*?)\n\}" % name, src, re.S)
+        assert len(body.strip().splitlines()) <= 3 and "row_total(" in body, (name, body)
+    block = open(os.path.join(sidelib.HERE, "common", "hier_block.h")).read()
+    assert block.count("void row_total(") == 1 and "__forceinline__ void row_total(" in block
 
 
 def _row(**kw):
