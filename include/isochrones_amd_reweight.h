@@ -102,6 +102,22 @@ int iso_reweight_stars_host(const iso_hier_column* columns, int32_t Q, const iso
                             double* ess, int32_t* n_bad, double* mean, double* sd, double* quant, int32_t* n_nan,
                             void* stream);
 
+/* The summaries alone, of weights the caller supplies (iso_shrink_weights's, for a binned population density): the
+ * "Per (star, value column)" paragraph above with u = weights, by k_reweight_summary as iso_reweight_stars launches it, so
+ * fed the weights that call wrote it returns that call's mean, sd, quant and n_nan bit for bit.  values ([V]): a host array of
+ * descriptors whose base pointers are device pointers.  probs ([K]): host.  mask ([n_ens] int32, or NULL), weights
+ * ([n_ens_out][M], numbered from ens_begin: an input), mean, sd ([n_ens][V]), quant ([n_ens][V][K]), n_nan ([n_ens][V]
+ * int32): device pointers.  A masked star's weights are not read. */
+int iso_reweight_summary(const iso_hier_column* values, int32_t V, int layout, int64_t nsteps, int32_t n_ens, int32_t W,
+                         int32_t ens_begin, int32_t n_ens_out, const int32_t* mask, const double* probs, int32_t K,
+                         const double* weights, double* mean, double* sd, double* quant, int32_t* n_nan, void* stream);
+
+/* the same on host pointers, by iso_reweight_stars_host's loops */
+int iso_reweight_summary_host(const iso_hier_column* values, int32_t V, int layout, int64_t nsteps, int32_t n_ens, int32_t W,
+                              int32_t ens_begin, int32_t n_ens_out, const int32_t* mask, const double* probs, int32_t K,
+                              const double* weights, double* mean, double* sd, double* quant, int32_t* n_nan,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

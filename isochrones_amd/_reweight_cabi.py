@@ -14,7 +14,8 @@ ERR_HIP = -2
 MAX_VALUES = 8
 MAX_PROBS = 8
 ROW_TILE = 64
-EXPORTED_SYMBOLS = ("iso_reweight_version", "iso_reweight_last_error", "iso_reweight_stars", "iso_reweight_stars_host")
+EXPORTED_SYMBOLS = ("iso_reweight_version", "iso_reweight_last_error", "iso_reweight_stars", "iso_reweight_stars_host",
+                    "iso_reweight_summary", "iso_reweight_summary_host")
 
 
 def _declare(L):
@@ -23,6 +24,10 @@ def _declare(L):
         fn.restype = C.c_int
         fn.argtypes = [col, C.c_int32, col, C.c_int32, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                        vp, vp, C.c_int32, vp, vp, C.POINTER(C.c_double), C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    for fn in (L.iso_reweight_summary, L.iso_reweight_summary_host):
+        fn.restype = C.c_int
+        fn.argtypes = [col, C.c_int32, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp,
+                       C.POINTER(C.c_double), C.c_int32, vp, vp, vp, vp, vp, vp]
 
 
 _SIDE = SideLibrary("reweight", "star reweighting", _declare, label="reweight")

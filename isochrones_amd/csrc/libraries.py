@@ -1,9 +1,9 @@
 """The side libraries, each a spec for sidelib.KernelLibrary, in the order __graft_entry__.build() builds them
-(BUILD_ORDER + ADDED + NEWER).
+(BUILD_ORDER + ADDED + NEWER + LATEST).
 
     python -m isochrones_amd.csrc.libraries NAME [--force] [--verbose]
 
-A new library is one more spec here (and its name in NEWER), its sources in csrc/<name>/ and its header
+A new library is one more spec here (and its name in LATEST), its sources in csrc/<name>/ and its header
 include/isochrones_amd_<name>.h."""
 from __future__ import annotations
 
@@ -211,6 +211,30 @@ BINNED = KernelLibrary(
     #: k_binned_total is k_hier_total: 17 VGPRs at 8 waves
     max_vgpr=96, min_waves=5, extra_headers=_RECORD_HEADERS + _COLUMN_HEADERS + ("common/hier_block.h",))
 
+# the per-star counterpart of BINNED (csrc/shrink/): every star's weights and bin memberships once a fitted histogram
+# replaces the interim prior.  The sum over the hyper rows belongs to the (star, cell), so it is taken once from BINNED's
+# tables, and the chain is read once with one exp per sample whatever the number of rows.  It reads HIER's records and
+# columns and BINNED's constants (its header includes both) and evaluates the per-sample term through
+# common/binned_sample.h, a restatement of binned.hip's (BINNED's header list is pinned; moving it over is the follow-up)
+# -ffp-contract=off: the compiler fuses nothing, and the sources write no fma(): every product and every sum of the header's
+# definition is rounded on its own (a star's outputs are bit-identical alone, in any batch, star range and layout, a (star,
+# cell) result in any block of stars and any tile of cells)
+SHRINK = KernelLibrary(
+    name="shrink", flags=_NO_CONTRACT,
+    #: every kernel the library compiles (tests/test_shrink_library.py pins this set)
+    kernels=("k_shrink_cells", "k_shrink_weights"),
+    #: k_shrink_weights compiles to 82 VGPRs, no scratch, 1.9 KB of LDS (the records, the edges, the star's lnG) and 5 waves per
+    #: SIMD: k_binned_compress's per-sample work (one column at a time, one inlined family evaluation, the bracket search)
+    #: with one exp on top and without the second pass's tile.  Its 10 spilled SGPRs (the argument block) go to VGPR lanes, not
+    #: to scratch.  The budget is what it compiles to, the 5-waves-per-SIMD one: 96 VGPRs, and no scratch at all.
+    #: k_shrink_cells is 62 VGPRs at 8 waves with 8 KB of LDS, at a tile of 2 cells.  The compiler hoists the constants of exp
+    #: and log to the kernel's top, 30 VGPRs that stay live throughout, so a tile's maxima and sums next to them decide the
+    #: occupancy: with a tile of 8 in registers it is 95 VGPRs (5 waves), with 4 in registers 78 (6 waves), with 4 parked in
+    #: LDS between the passes 69 (7 waves); held to 64 VGPRs those spill 124, 60 and 12 bytes to scratch.  The tile only
+    #: sets how often ell is read again (B / 2 times two passes), next to one exp per (row, cell)
+    max_vgpr=96, min_waves=5,
+    extra_headers=("../../include/isochrones_amd_binned.h",) + _RECORD_HEADERS + _COLUMN_HEADERS + ("common/binned_sample.h",))
+
 #: the six libraries the shared builder started with (tests/test_side_libraries_cpu.py pins this tuple to exactly these)
 ALL = (CLUSTER, NESTED, SOLVE, DIAG, DERIVED, PREDICT)
 #: what __graft_entry__.build() and the command line below build, in order: ALL and the libraries added since ALL was
@@ -223,10 +247,14 @@ ADDED = (HIER,)
 #: command line below go through BUILD_ORDER + ADDED + NEWER.  The next library goes here: its test asserts membership,
 #: not equality, so this tuple grows
 NEWER = (SELECT, REWEIGHT, RELATION, BINNED)
+#: the libraries added after NEWER was pinned in its turn (tests/test_side_libraries_cpu.py names its members);
+#: __graft_entry__.build() and the command line below go through BUILD_ORDER + ADDED + NEWER + LATEST.  The next library goes
+#: here: tests/test_shrink_library.py asserts membership, not equality, so this tuple grows
+LATEST = (SHRINK,)
 
 
 if __name__ == "__main__":
-    by_name = {spec.name: spec for spec in BUILD_ORDER + ADDED + NEWER}
+    by_name = {spec.name: spec for spec in BUILD_ORDER + ADDED + NEWER + LATEST}
     names = [a for a in sys.argv[1:] if not a.startswith("--")]
     if len(names) != 1 or names[0] not in by_name:
         sys.exit("usage: python -m isochrones_amd.csrc.libraries {%s} [--force] [--verbose]" % ",".join(by_name))

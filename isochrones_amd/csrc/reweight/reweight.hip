@@ -371,6 +371,119 @@ int check_args(const char* who, const iso_hier_column* columns, int32_t Q, const
     return why ? fail(ISO_REWEIGHT_ERR_INVALID, who, why) : 0;
 }
 
+// the checks of iso_reweight_summary: check_args's, of what the summaries alone take
+int check_summary(const char* who, const iso_hier_column* values, int32_t V, int layout, int64_t nsteps, int32_t n_ens,
+                  int32_t W, int32_t ens_begin, int32_t n_ens_out, const double* probs, int32_t K, const double* weights,
+                  const double* mean, const double* sd, const double* quant, const int32_t* n_nan) {
+    ChainShape s{layout, nsteps, n_ens, W, 1};
+    s.ens_begin = ens_begin;
+    s.n_ens_out = n_ens_out;
+    const char* why = nullptr;
+    if (!values || !probs || !weights || !mean || !sd || !quant || !n_nan) why = "null pointer";
+    else if (V < 1 || V > MAXV) why = "V must be 1 to 8 value columns";
+    else if (K < 1 || K > MAXK) why = "K must be 1 to 8 probabilities";
+    else if ((why = chain_shape_error(CHAIN_CHECK_LAYOUT | CHAIN_CHECK_SIZES | CHAIN_CHECK_RANGE | CHAIN_CHECK_ROWS, s))) {}
+    else if (nsteps * (int64_t)W > INT32_MAX) why = "more than 2^31 - 1 samples per star (thin the chain)";
+    else if ((int64_t)n_ens_out * V > INT32_MAX) why = "more than 2^31 - 1 (star, value column) pairs (split the call)";
+    else {
+        for (int k = 0; k < K && !why; ++k)
+            if (!(probs[k] > 0.0 && probs[k] < 1.0)) why = "a probability is outside (0, 1)";
+        for (int v = 0; v < V && !why; ++v) why = column_error(values[v], W, ens_begin, n_ens_out);
+    }
+    return why ? fail(ISO_REWEIGHT_ERR_INVALID, who, why) : 0;
+}
+
+// k_reweight_summary on the weights of the stars [ens_begin, ens_begin + n_ens_out): the second launch of
+// iso_reweight_stars and the only one of iso_reweight_summary
+int launch_summary(const iso_hier_column* values, int32_t V, int layout, int64_t nsteps, int32_t W, int32_t ens_begin,
+                   int32_t n_ens_out, const int32_t* mask, const double* probs, int32_t K, const double* weights,
+                   double* mean, double* sd, double* quant, int32_t* n_nan, void* stream) {
+    SArgs B;
+    for (int v = 0; v < MAXV; ++v) B.val[v] = dev_col(values[v < V ? v : 0], layout, W);
+    for (int k = 0; k < MAXK; ++k) B.probs[k] = probs[k < K ? k : 0];
+    B.weights = weights;
+    B.mask = mask;
+    B.mean = mean;
+    B.sd = sd;
+    B.quant = quant;
+    B.n_nan = n_nan;
+    B.V = V;
+    B.K = K;
+    B.T = (int32_t)nsteps;
+    B.W = W;
+    B.ens_begin = ens_begin;
+    B.pad = 0;
+    hipLaunchKernelGGL(k_reweight_summary, dim3((unsigned)n_ens_out * (unsigned)V), dim3(BLOCK), 0, (hipStream_t)stream, B);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ISO_REWEIGHT_ERR_HIP, hipGetErrorString(e));
+    return 0;
+}
+
+// the summaries of a masked star
+void summary_masked_host(int s, int V, int K, double* mean, double* sd, double* quant, int32_t* n_nan) {
+    for (int v = 0; v < V; ++v) {
+        const size_t at = (size_t)s * V + v;
+        mean[at] = sd[at] = qnan();
+        n_nan[at] = 0;
+        for (int k = 0; k < K; ++k) quant[at * K + k] = qnan();
+    }
+}
+
+// the summaries of the unmasked star s under its weights u[0 .. M), with plain ascending loops and a stable sort; y, uy
+// ([M]) and order are the caller's, so that a call allocates them once
+void summary_star_host(const DevCol* val, int V, int K, const double* probs, int s, int W, int M, const double* u,
+                       double* mean, double* sd, double* quant, int32_t* n_nan, std::vector<double>& y,
+                       std::vector<double>& uy, std::vector<int>& order) {
+    for (int v = 0; v < V; ++v) {
+        const DevCol& c = val[v];
+        const size_t at = (size_t)s * V + v;
+        double tot = 0.0, sy = 0.0;
+        int nn = 0;
+        for (int m = 0; m < M; ++m) {
+            const int t = m / W, w = m - t * W;
+            const double y0 = load(c, s, W, t, w);
+            const bool isn = y0 != y0;
+            nn += isn ? 1 : 0;
+            y[m] = isn ? 0.0 : y0 + 0.0;
+            uy[m] = isn ? 0.0 : u[m];
+            tot += uy[m];
+            sy += uy[m] * y[m];
+        }
+        n_nan[at] = nn;
+        if (!(tot > 0.0) || tot == HUGE_VAL) {
+            mean[at] = sd[at] = qnan();
+            for (int k = 0; k < K; ++k) quant[at * K + k] = qnan();
+            continue;
+        }
+        const double mu = sy / tot;
+        double q2 = 0.0;
+        for (int m = 0; m < M; ++m) {
+            const double d = y[m] - mu;
+            q2 += uy[m] * (d * d);
+        }
+        mean[at] = mu;
+        sd[at] = sqrt(q2 / tot);
+        // the samples of positive weight in ascending y, equal values in sample order
+        order.clear();
+        for (int m = 0; m < M; ++m)
+            if (uy[m] > 0.0) order.push_back(m);
+        std::stable_sort(order.begin(), order.end(), [&](int i, int j) { return y[i] < y[j]; });
+        for (int k = 0; k < K; ++k) {
+            const double target = probs[k] * tot;
+            double cum = 0.0, ystar = y[order.back()];
+            for (size_t i = 0; i < order.size(); ++i) {
+                cum += uy[order[i]];
+                const bool group_end = i + 1 == order.size() || y[order[i + 1]] != y[order[i]];
+                if (group_end && cum >= target) {
+                    ystar = y[order[i]];
+                    break;
+                }
+            }
+            quant[at * K + k] = ystar;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -405,27 +518,10 @@ int iso_reweight_stars(const iso_hier_column* columns, int32_t Q, const iso_hier
     A.n_ens = n_ens;
     A.ens_begin = ens_begin;
     hipLaunchKernelGGL(k_reweight_weights, dim3((unsigned)n_ens_out), dim3(BLOCK), 0, (hipStream_t)stream, A);
-    hipError_t e = hipGetLastError();
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(ISO_REWEIGHT_ERR_HIP, hipGetErrorString(e));
-    SArgs B;
-    for (int v = 0; v < MAXV; ++v) B.val[v] = dev_col(values[v < V ? v : 0], layout, W);
-    for (int k = 0; k < MAXK; ++k) B.probs[k] = probs[k < K ? k : 0];
-    B.weights = weights;
-    B.mask = mask;
-    B.mean = mean;
-    B.sd = sd;
-    B.quant = quant;
-    B.n_nan = n_nan;
-    B.V = V;
-    B.K = K;
-    B.T = (int32_t)nsteps;
-    B.W = W;
-    B.ens_begin = ens_begin;
-    B.pad = 0;
-    hipLaunchKernelGGL(k_reweight_summary, dim3((unsigned)n_ens_out * (unsigned)V), dim3(BLOCK), 0, (hipStream_t)stream, B);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(ISO_REWEIGHT_ERR_HIP, hipGetErrorString(e));
-    return 0;
+    return launch_summary(values, V, layout, nsteps, W, ens_begin, n_ens_out, mask, probs, K, weights, mean, sd, quant, n_nan,
+                          stream);
 }
 
 int iso_reweight_stars_host(const iso_hier_column* columns, int32_t Q, const iso_hier_column* values, int32_t V, int layout,
@@ -450,12 +546,7 @@ int iso_reweight_stars_host(const iso_hier_column* columns, int32_t Q, const iso
         if (mask && mask[s] == 0) {
             wsum[s] = ess[s] = qnan();
             n_bad[s] = 0;
-            for (int v = 0; v < V; ++v) {
-                const size_t at = (size_t)s * V + v;
-                mean[at] = sd[at] = qnan();
-                n_nan[at] = 0;
-                for (int k = 0; k < K; ++k) quant[at * K + k] = qnan();
-            }
+            summary_masked_host(s, V, K, mean, sd, quant, n_nan);
             continue;
         }
         double* const u = weights + (size_t)(s - ens_begin) * (size_t)M;
@@ -492,54 +583,43 @@ int iso_reweight_stars_host(const iso_hier_column* columns, int32_t Q, const iso
         wsum[s] = S1;
         ess[s] = (S1 == 0.0) ? 0.0 : (S1 * S1) / S2;
         n_bad[s] = nb;
-        for (int v = 0; v < V; ++v) {
-            const DevCol& c = val[v];
-            const size_t at = (size_t)s * V + v;
-            double tot = 0.0, sy = 0.0;
-            int nn = 0;
-            for (int m = 0; m < M; ++m) {
-                const int t = m / W, w = m - t * W;
-                const double y0 = load(c, s, W, t, w);
-                const bool isn = y0 != y0;
-                nn += isn ? 1 : 0;
-                y[m] = isn ? 0.0 : y0 + 0.0;
-                uy[m] = isn ? 0.0 : u[m];
-                tot += uy[m];
-                sy += uy[m] * y[m];
-            }
-            n_nan[at] = nn;
-            if (!(tot > 0.0) || tot == HUGE_VAL) {
-                mean[at] = sd[at] = qnan();
-                for (int k = 0; k < K; ++k) quant[at * K + k] = qnan();
-                continue;
-            }
-            const double mu = sy / tot;
-            double q2 = 0.0;
-            for (int m = 0; m < M; ++m) {
-                const double d = y[m] - mu;
-                q2 += uy[m] * (d * d);
-            }
-            mean[at] = mu;
-            sd[at] = sqrt(q2 / tot);
-            // the samples of positive weight in ascending y, equal values in sample order
-            order.clear();
-            for (int m = 0; m < M; ++m)
-                if (uy[m] > 0.0) order.push_back(m);
-            std::stable_sort(order.begin(), order.end(), [&](int i, int j) { return y[i] < y[j]; });
-            for (int k = 0; k < K; ++k) {
-                const double target = probs[k] * tot;
-                double cum = 0.0, ystar = y[order.back()];
-                for (size_t i = 0; i < order.size(); ++i) {
-                    cum += uy[order[i]];
-                    const bool group_end = i + 1 == order.size() || y[order[i + 1]] != y[order[i]];
-                    if (group_end && cum >= target) {
-                        ystar = y[order[i]];
-                        break;
-                    }
-                }
-                quant[at * K + k] = ystar;
-            }
+        summary_star_host(val, V, K, probs, s, W, M, u, mean, sd, quant, n_nan, y, uy, order);
+    }
+    return 0;
+}
+
+int iso_reweight_summary(const iso_hier_column* values, int32_t V, int layout, int64_t nsteps, int32_t n_ens, int32_t W,
+                         int32_t ens_begin, int32_t n_ens_out, const int32_t* mask, const double* probs, int32_t K,
+                         const double* weights, double* mean, double* sd, double* quant, int32_t* n_nan, void* stream) {
+    g_err[0] = 0;
+    const int rc = check_summary("iso_reweight_summary", values, V, layout, nsteps, n_ens, W, ens_begin, n_ens_out, probs, K,
+                                 weights, mean, sd, quant, n_nan);
+    if (rc) return rc;
+    return launch_summary(values, V, layout, nsteps, W, ens_begin, n_ens_out, mask, probs, K, weights, mean, sd, quant, n_nan,
+                          stream);
+}
+
+int iso_reweight_summary_host(const iso_hier_column* values, int32_t V, int layout, int64_t nsteps, int32_t n_ens, int32_t W,
+                              int32_t ens_begin, int32_t n_ens_out, const int32_t* mask, const double* probs, int32_t K,
+                              const double* weights, double* mean, double* sd, double* quant, int32_t* n_nan,
+                              void* stream) {
+    (void)stream;
+    g_err[0] = 0;
+    const int rc = check_summary("iso_reweight_summary_host", values, V, layout, nsteps, n_ens, W, ens_begin, n_ens_out, probs,
+                                 K, weights, mean, sd, quant, n_nan);
+    if (rc) return rc;
+    DevCol val[MAXV];
+    for (int v = 0; v < V; ++v) val[v] = dev_col(values[v], layout, W);
+    const int M = (int)nsteps * W;
+    std::vector<double> y(M), uy(M);
+    std::vector<int> order;
+    for (int s = ens_begin; s < ens_begin + n_ens_out; ++s) {
+        if (mask && mask[s] == 0) {
+            summary_masked_host(s, V, K, mean, sd, quant, n_nan);
+            continue;
         }
+        summary_star_host(val, V, K, probs, s, W, M, weights + (size_t)(s - ens_begin) * (size_t)M, mean, sd, quant, n_nan,
+                          y, uy, order);
     }
     return 0;
 }

@@ -454,8 +454,6 @@ class PopulationPosterior:
         return ", ".join("%s on %s" % (c, m.columns[p]) for c, p in zip(m.columns, m.parents) if p >= 0)
 
     def _uncoupled(self, what):
-        if self.model.binned:
-            raise NotImplementedError("%s on a binned population model is not built yet" % what)
         if self.model.coupled:
             raise ValueError("%s needs an uncoupled population model: the reweighting library evaluates one-column "
                              "families only and has no kernel for a linked one (%s)" % (what, self._links()))
@@ -671,7 +669,9 @@ class PopulationPosterior:
         DataFrame (``as_tensors=True``: a dict of tensors where the chain lies) with one row per star: per column
         ``{col}_median, _p16, _p84`` (``_q<100 p>`` for another q), ``{col}_mean``, ``{col}_sd``, then ``ess`` (the effective
         sample size of the star's weights) and ``n_bad``.  A masked star is NaN; so are the column summaries of a star with
-        no weight left (its ``ess`` is 0)."""
+        no weight left (its ``ess`` is 0).  On a binned model (a Histogram) the kernels are libiso_shrink.so's, the weights
+        are computed once per slice of stars whatever the number of rows, and the frame has ``n_out`` next to ``n_bad``: the
+        star's good samples outside the grid of bins, which weigh nothing."""
         from . import reweight
         self._uncoupled("star_posteriors")
         return reweight.star_posteriors(self, theta, columns, q, as_tensors)
@@ -683,6 +683,15 @@ class PopulationPosterior:
         from . import reweight
         self._uncoupled("star_weights")
         return reweight.star_weights(self, theta, stars)
+
+    def star_bin_probabilities(self, theta=None):
+        """The posterior probability of every star lying in each cell of a binned model's grid, ``[S, B]`` (``[S, K0, K1]``
+        for two binned columns, the parent's bins first), where the chain lies: which age bin a star is in once the fitted
+        histogram replaces the interim prior.  From the per-star tables alone, without reading the chain again
+        (``iso_shrink_cells``).  ``theta``: as in :meth:`star_posteriors`.  A star's row sums to 1; a masked star and a star
+        with no weight left are NaN.  A model without a Histogram raises ``ValueError``."""
+        from . import reweight
+        return reweight.bin_probabilities(self, theta)
 
     def lnprior(self, theta):
         lp = self.model.lnprior(theta.detach().cpu().numpy() if dev.is_tensor(theta) else np.atleast_2d(theta))
