@@ -32,5 +32,7 @@ from . import relations
 from .relations import LinearGaussian
 from . import binned
 from .binned import Histogram
+from . import draws
+from .draws import DrawPlan
 
 __version__ = "0.1.0"

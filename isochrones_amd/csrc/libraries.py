@@ -235,6 +235,24 @@ SHRINK = KernelLibrary(
     max_vgpr=96, min_waves=5,
     extra_headers=("../../include/isochrones_amd_binned.h",) + _RECORD_HEADERS + _COLUMN_HEADERS + ("common/binned_sample.h",))
 
+# random draws of synthetic populations and injection sets (csrc/draw/): every column of every system from counter-based
+# uniforms (Philox4x32-10, common/philox.h) through an exact inverse distribution function (ndtri: common/ndtri.h).  It
+# shares no record with the other libraries: a draw record carries the thresholds of an inverse, not a log density
+# -ffp-contract=off: the compiler fuses nothing, and the sources write no fma(): every product and every sum of the header's
+# definition is rounded on its own (a system's draws are bit-identical alone, in any batch, at any first and through index)
+DRAW = KernelLibrary(
+    name="draw", flags=_NO_CONTRACT,
+    #: every kernel the library compiles (tests/test_draw_library.py pins this set)
+    kernels=("k_draw_systems",),
+    #: k_draw_systems compiles to 127 VGPRs, no scratch, no LDS and 4 waves per SIMD, asked for by its launch bounds.  Left
+    #: alone the compiler takes 185 VGPRs (2 waves): it interleaves the ten Philox rounds with the constants of erfc, exp,
+    #: log1p and ndtri's three rational functions, all inlined into one loop body, and none of that needs to be live at once.
+    #: A lane holds the system's eight values (16 registers), the two uniforms and one inverse at a time.  The kernel writes
+    #: 8 bytes per (system, column) next to some hundred integer and float64 operations, with no load to wait for, so the
+    #: waves only have to cover the arithmetic's own latency; the budget is the 4-waves-per-SIMD one: 128 VGPRs, and no scratch
+    #: at all.  Its 17 spilled SGPRs (a record of the argument block) go to VGPR lanes, not to scratch
+    max_vgpr=128, min_waves=4, extra_headers=("common/last_error.h", "common/ndtri.h", "common/philox.h"))
+
 #: the six libraries the shared builder started with (tests/test_side_libraries_cpu.py pins this tuple to exactly these)
 ALL = (CLUSTER, NESTED, SOLVE, DIAG, DERIVED, PREDICT)
 #: what __graft_entry__.build() and the command line below build, in order: ALL and the libraries added since ALL was
@@ -250,7 +268,7 @@ NEWER = (SELECT, REWEIGHT, RELATION, BINNED)
 #: the libraries added after NEWER was pinned in its turn (tests/test_side_libraries_cpu.py names its members);
 #: __graft_entry__.build() and the command line below go through BUILD_ORDER + ADDED + NEWER + LATEST.  The next library goes
 #: here: tests/test_shrink_library.py asserts membership, not equality, so this tuple grows
-LATEST = (SHRINK,)
+LATEST = (SHRINK, DRAW)
 
 
 if __name__ == "__main__":

@@ -325,6 +325,42 @@ class PopulationModel:
             k += len(fam.names)
         return out
 
+    def draw_plan(self, theta):
+        """The :class:`isochrones_amd.draws.DrawPlan` of the model at one row ``theta`` [P] of its hyper-parameters: a column
+        per family, a LinearGaussian after the column it follows, a Histogram as a table of its bin masses (the cell
+        densities of :meth:`cell_table` times the bin widths; ``given=``: one row of masses per bin of the parent)."""
+        from . import draws
+        theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(-1)
+        if theta.size != self.n_params:
+            raise ValueError("theta must be one row of %d hyper-parameters (%s)" % (self.n_params, ", ".join(self.param_names)))
+        start = np.concatenate([[0], np.cumsum([len(f.names) for f in self.families])]).astype(int)
+        cols = {}
+        mass = None
+        if self.binned:
+            ct = self.cell_table(theta[None, :])
+            widths = [np.diff(e) for e in ct["edges"]]
+            with np.errstate(all="ignore"):
+                mass = np.exp(ct["lnh"][0]).reshape([w.size for w in widths])
+            mass = mass * (widths[0] if len(widths) == 1 else widths[0][:, None] * widths[1][None, :])
+        for q, (col, fam) in enumerate(zip(self.columns, self.families)):
+            if not isinstance(fam, _Binned):
+                cols[col] = draws.bound(fam, theta[start[q]:start[q + 1]])
+            elif len(self.axes) == 1:
+                cols[col] = draws.table(fam.edges, mass)
+            elif q == self.axes[0]:
+                cols[col] = draws.table(fam.edges, mass.sum(axis=1))
+            elif fam.given is not None:
+                cols[col] = draws.table(fam.edges, mass, given=fam.given, parent_edges=self.families[self.axes[0]].edges)
+            else:
+                cols[col] = draws.table(fam.edges, mass.sum(axis=0))
+        return draws.DrawPlan(cols)
+
+    def sample(self, theta, n, seed=0, device=None):
+        """``{column: [n]}``: ``n`` systems drawn from the population density at one row ``theta`` of the hyper-parameters, by
+        ``iso_draw_systems`` on ``device`` (CUDA tensors) or, with ``device=None``, by its host entry (numpy arrays): a
+        synthetic catalog to check a fit against, or the columns of an injection set drawn near the fitted density."""
+        return self.draw_plan(theta).draw(n, seed, device=device)
+
     def lnprior(self, theta):
         """The flat hyper-prior over the free ranges: -sum ln(width) inside, -inf outside; numpy [H]."""
         theta = np.asarray(theta, dtype=np.float64)

@@ -3,8 +3,9 @@ companions from a binary fraction and a mass-ratio law, ages from a star-formati
 evaluates all systems in one launch of the HIP kernel of libiso_population.so (``iso_population_eval``; the definition
 is in include/isochrones_amd_population.h): per component the model columns, the magnitudes and the per-band
 extinctions, per system the combined magnitudes and extinctions - the reference's ``generate_binary(..., all_As=True)``.
-The draws are made on the host with one seeded ``numpy.random.Generator``; the EEPs come from the device paths that exist
-(``ic.get_eep`` / ``ic.solve_eep`` on CUDA tensors)."""
+The draws are made on the host with one seeded ``numpy.random.Generator`` or, with ``rng="philox"``, where the systems are
+evaluated by libiso_draw.so (:mod:`isochrones_amd.draws`); the EEPs come from the device paths that exist (``ic.get_eep`` /
+``ic.solve_eep`` on CUDA tensors)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -345,24 +346,72 @@ class StarPopulation:
         av = _sample(self.AV, N, rng) if hasattr(self.AV, "sample") else np.full(N, float(self.AV))
         return masses, secondary, ages, fehs, dist, av
 
-    def generate(self, N, accurate=False, exact_N=True, seed=None, as_tensors=False, **kwargs):
+    #: the columns of the Philox plan and their streams: a column keeps its number whatever the others are
+    PHILOX_COLUMNS = ("mass", "binary", "q", "age", "feh", "distance", "AV")
+
+    def draw_plan(self):
+        """The :class:`isochrones_amd.draws.DrawPlan` of ``generate(rng="philox")``: primary mass, a uniform on (0, 1) that
+        is compared with ``fB``, mass ratio, log10 age, [Fe/H], distance, AV.  A distribution the device has no inverse for
+        (a ``StarFormationHistoryGrid``, a scipy distribution that is not uniform) is a host column."""
+        from . import draws
+        from .priors import FlatPrior
+
+        class _Ages:                                            # a star-formation history as a host column: log10 years
+            def __init__(self, sfh):
+                self.sfh = sfh
+
+            def sample(self, n, rng=None):
+                return self.sfh.sample_ages(n, rng)
+
+        sfh = self.sfh
+        plain = type(sfh) is StarFormationHistory and draws._is_scipy_uniform(sfh.dist)
+        cols = {"mass": self.imf, "binary": FlatPrior((0.0, 1.0)), "q": self.binary_distribution.mass_ratio_distribution,
+                "age": sfh.dist if plain else _Ages(sfh), "feh": self.feh,
+                "distance": self.distance if hasattr(self.distance, "sample") else float(self.distance),
+                "AV": self.AV if hasattr(self.AV, "sample") else float(self.AV)}
+        return draws.DrawPlan(cols, streams={name: k for k, name in enumerate(self.PHILOX_COLUMNS)})
+
+    def _philox_evaluator(self, seed, accurate, kwargs):
+        """``evaluate(n, round, bad)`` of :meth:`generate` with the draws of :meth:`draw_plan`: the first round draws the
+        systems 0 .. n - 1, a later one exactly the systems ``bad`` marks, through ``index``."""
+        bk = kwargs["_backend"] if kwargs["_backend"] is not None else _DeviceBackend(dev.current_device())
+        plan = self.draw_plan()
+        device = None if isinstance(bk, _HostBackend) else bk.device
+        seed = 0 if seed is None else int(seed)
+
+        def evaluate(n, rnd, bad):
+            index = None if bad is None else (bad.nonzero().reshape(-1) if dev.is_tensor(bad) else np.flatnonzero(bad))
+            d = plan.draw(n, seed, round=rnd, index=index, device=device)
+            secondary = d["q"] * d["mass"] * (d["binary"] < self.fB)
+            return _evaluate(self.ic, d["mass"], secondary, d["age"], d["feh"], d["distance"], d["AV"], kwargs.get("bands"),
+                             kwargs.get("props", "all"), accurate, None, bk)
+
+        return evaluate
+
+    def generate(self, N, accurate=False, exact_N=True, seed=None, as_tensors=False, rng="numpy", **kwargs):
         """``N`` systems as a DataFrame with the reference's columns in the reference's order (``as_tensors=True``: the dict
         of CUDA tensors instead).  The draws come from ``numpy.random.default_rng(seed)``.  ``exact_N=True`` redraws the
         systems whose primary fell off the model grid (``mass_0`` NaN) and evaluates them again, a smaller batch each round,
         at most ``MAX_REDRAW_ROUNDS`` times; ``exact_N=False`` drops them.  Other keywords (``bands=``, ``props=``) go to
-        :func:`evaluate_binaries`."""
+        :func:`evaluate_binaries`.  ``rng="philox"`` draws where the systems are evaluated (:meth:`draw_plan`, ``seed=None``
+        is 0): system j is then the same whatever ``N``, and ``exact_N`` redraws exactly the systems off the grid."""
         N = int(N)
-        rng = np.random.default_rng(seed)
+        if rng not in ("numpy", "philox"):
+            raise ValueError("rng is 'numpy' or 'philox'")
         kwargs.setdefault("_backend", self._backend)
-
-        def evaluate(n):
-            return _evaluate(self.ic, *self.draw(n, rng), kwargs.get("bands"), kwargs.get("props", "all"), accurate, None,
-                             kwargs["_backend"])
-
         unknown = set(kwargs) - {"bands", "props", "_backend"}
         if unknown:
             raise TypeError("generate() got unexpected keywords %s" % sorted(unknown))
-        pop = evaluate(N)
+        if rng == "philox":
+            evaluate = self._philox_evaluator(seed, accurate, kwargs)
+        else:
+            gen = np.random.default_rng(seed)
+
+            def evaluate(n, rnd, bad):
+                return _evaluate(self.ic, *self.draw(n, gen), kwargs.get("bands"), kwargs.get("props", "all"), accurate, None,
+                                 kwargs["_backend"])
+
+        pop = evaluate(N, 0, None)
         if "mass_0" not in pop.columns:
             raise ValueError("props must include 'mass' (rows off the grid are found by mass_0)")
         bk = pop.backend
@@ -375,7 +424,7 @@ class StarPopulation:
                                        "rounds of redrawing - the distributions do not reach the grid (exact_N=False "
                                        "returns the rows that do)" % (bk.count(bad), N, rounds))
                 rounds += 1
-                pop.matrix[:, bad] = evaluate(bk.count(bad)).matrix
+                pop.matrix[:, bad] = evaluate(bk.count(bad), rounds, bad).matrix
                 bad = bk.isnan(pop.row("mass_0"))
         elif bk.any(bad):
             pop = _Evaluated(bk, pop.columns, bk.take(pop.matrix, ~bad))

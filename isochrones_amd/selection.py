@@ -88,8 +88,10 @@ class InjectionSet:
         #: injections off the model or BC grid (:meth:`draw` counts them; they are undetected and stay in J)
         self.n_off = n_off
 
+    _backend = None                                             # (the CPU tests route the evaluation to the host entries)
+
     @classmethod
-    def draw(cls, ic, draw, n, limits, seed=None, accurate="exact"):
+    def draw(cls, ic, draw, n, limits, seed=None, accurate="exact", rng="numpy"):
         """``n`` single stars drawn on the host from ``draw`` = ``{column: prior}`` (``mass``, ``age``, ``feh`` and
         optionally ``distance``, ``AV``; one ``numpy.random.default_rng(seed)``, ``prior.sample(n, rng)`` in the order of
         ``draw``), evaluated on the model and BC grid by :func:`isochrones_amd.populations.evaluate_binaries` (one EEP solve,
@@ -97,7 +99,8 @@ class InjectionSet:
         band's term of ``lnd`` is ``log_ndtr((limit - mag) / sigma)``, the chance that a magnitude observed with Gaussian
         noise sigma passes; with sigma = 0 it is 0 where ``mag <= limit`` and -inf elsewhere.  The terms are added over
         the bands in the order given.  An injection off the grid (a NaN magnitude) is a star that cannot be observed:
-        ``lnd`` = -inf; ``n_off`` counts them."""
+        ``lnd`` = -inf; ``n_off`` counts them.  ``rng="philox"`` draws the columns on the device instead
+        (:class:`isochrones_amd.draws.DrawPlan`, ``seed=None`` is 0): they never visit the host."""
         from .populations import evaluate_binaries
         draw = dict(draw)
         for name in draw:
@@ -113,12 +116,25 @@ class InjectionSet:
                 raise ValueError("the sigma of band %r must be 0 or positive" % (band,))
         records = {name: prior_record(p) for name, p in draw.items()}          # refuses a host-evaluated prior before any work
         del records
-        rng = np.random.default_rng(seed)
-        cols = {name: np.ascontiguousarray(p.sample(int(n), rng), dtype=np.float64) for name, p in draw.items()}
+        if rng not in ("numpy", "philox"):
+            raise ValueError("rng is 'numpy' or 'philox'")
+        on_host = getattr(cls._backend, "device", None) == "host"
+        if rng == "philox":
+            from .draws import DrawPlan
+            streams = {name: k for k, name in enumerate(_TRACK_COLUMNS)}
+            cols = DrawPlan(draw, streams={name: streams[name] for name in draw}).draw(
+                int(n), 0 if seed is None else int(seed), device=None if on_host else dev.current_device())
+        else:
+            rng = np.random.default_rng(seed)
+            cols = {name: np.ascontiguousarray(p.sample(int(n), rng), dtype=np.float64) for name, p in draw.items()}
         args = {name: cols.get(name, default) for name, default in _TRACK_COLUMNS.items()}
         bands = tuple(limits)
         out = evaluate_binaries(ic, args["mass"], 0.0, args["age"], args["feh"], args["distance"], args["AV"], bands=bands,
-                                props=("mass",), accurate=accurate)
+                                props=("mass",), accurate=accurate, _backend=cls._backend)
+        if on_host:                                             # detection_lnd is stated in framework ops
+            import torch
+            lnd, off = detection_lnd({band: torch.from_numpy(np.ascontiguousarray(out["%s_mag" % band])) for band in bands}, limits)
+            return cls(cols, draw, lnd.numpy(), n_off=int(off.sum().item()))
         lnd, off = detection_lnd({band: out["%s_mag" % band] for band in bands}, limits)
         return cls(cols, draw, lnd, n_off=int(off.sum().item()))
 
