@@ -34,5 +34,7 @@ from . import binned
 from .binned import Histogram
 from . import draws
 from .draws import DrawPlan
+from . import binfit
+from .binfit import BinnedFit
 
 __version__ = "0.1.0"

@@ -253,6 +253,28 @@ DRAW = KernelLibrary(
     #: at all.  Its 17 spilled SGPRs (a record of the argument block) go to VGPR lanes, not to scratch
     max_vgpr=128, min_waves=4, extra_headers=("common/last_error.h", "common/ndtri.h", "common/philox.h"))
 
+# the moments of the stars' posterior cell probabilities under a binned population (csrc/binfit/): the expected number of
+# stars per cell and the sum of the outer products, per hyper row, from BINNED's per-star tables alone: the E-step of a
+# maximum-likelihood fit of the cell heights, the gradient and the curvature of BINNED's ln L.  It reads no record and no
+# chain; its header includes BINNED's for the limit of a grid
+# -ffp-contract=off: the compiler fuses nothing, and the sources write no fma(): every product and every sum of the header's
+# definition is rounded on its own (a row's outputs are bit-identical alone, in any sub-range of the rows and on every call)
+BINFIT = KernelLibrary(
+    name="binfit", flags=_NO_CONTRACT,
+    #: every kernel the library compiles (tests/test_binfit_library.py pins this set)
+    kernels=("k_binfit_partial", "k_binfit_total"),
+    #: k_binfit_partial compiles to 120 VGPRs, no scratch, 33.5 KB of LDS and 4 waves per SIMD.  A lane holds the sums of its
+    #: block of 3 x 3 pairs and of its cell (20 registers), the six places of the block's cells in a tile row, the sixteen
+    #: loads of its star's cells that a tile issues together (32, with their addresses) and, in the walk unrolled over two
+    #: stars, their twelve 64-bit LDS reads in flight (24).  The waves are set by the LDS, not by the registers: a tile of
+    #: 64 stars x 65 doubles lets four workgroups share a CU's 160 KB, which is four waves per SIMD, and at that occupancy a
+    #: lane may use 128 registers.  Carrying the next tile's sixteen values through the walk (a prefetch a tile ahead) takes
+    #: 138 to 152 registers, 3 waves, and held to 128 it spills 8 bytes to scratch: left out.  The budget is the
+    #: 4-waves-per-SIMD one: 128 VGPRs, and no scratch at all.
+    #: k_binfit_total (a running sum and the addresses of its two stores) is 14 VGPRs at 8 waves
+    max_vgpr=128, min_waves=4,
+    extra_headers=("../../include/isochrones_amd_binned.h", "../../include/isochrones_amd_hier.h", "common/last_error.h"))
+
 #: the six libraries the shared builder started with (tests/test_side_libraries_cpu.py pins this tuple to exactly these)
 ALL = (CLUSTER, NESTED, SOLVE, DIAG, DERIVED, PREDICT)
 #: what __graft_entry__.build() and the command line below build, in order: ALL and the libraries added since ALL was
@@ -268,7 +290,7 @@ NEWER = (SELECT, REWEIGHT, RELATION, BINNED)
 #: the libraries added after NEWER was pinned in its turn (tests/test_side_libraries_cpu.py names its members);
 #: __graft_entry__.build() and the command line below go through BUILD_ORDER + ADDED + NEWER + LATEST.  The next library goes
 #: here: tests/test_shrink_library.py asserts membership, not equality, so this tuple grows
-LATEST = (SHRINK, DRAW)
+LATEST = (SHRINK, DRAW, BINFIT)
 
 
 if __name__ == "__main__":

@@ -729,6 +729,39 @@ class PopulationPosterior:
         from . import reweight
         return reweight.bin_probabilities(self, theta)
 
+    # -- maximum likelihood for a binned model (isochrones_amd.binfit; the kernels of libiso_binfit.so) ---------------------
+    def cell_counts(self, theta, pairs=False):
+        """``(N [H, B], n_live [H])`` of a binned model under the rows ``theta`` [H, P], where ``theta`` lies: the expected
+        number of stars in every cell (the sum over the live stars of their posterior cell probabilities, for one row the
+        star-sum of :meth:`star_bin_probabilities`) and the number of live stars (unmasked, with weight under the row).
+        ``pairs=True``: ``(N, C [H, B, B], n_live)`` with ``C`` the sum of the outer products of the cell probabilities.
+        From the per-star tables alone (``iso_binfit_moments``).  A model without a Histogram raises ``ValueError``."""
+        from . import binfit
+        return binfit.cell_counts(self, theta, pairs)
+
+    def grad(self, theta):
+        """The derivative of :meth:`lnlike` with respect to every hyper-parameter of a binned model, ``[H, P]`` where
+        ``theta`` lies; with an injection set the selection term is included.  A model without a Histogram raises."""
+        from . import binfit
+        return binfit.grad(self, theta)
+
+    def hessian(self, theta):
+        """The second derivative of :meth:`lnlike` with respect to the hyper-parameters of a binned model, ``[H, P, P]``."""
+        from . import binfit
+        return binfit.hessian(self, theta)
+
+    def maximize(self, theta0=None, max_iter=2000, tol=1e-8, errors=True):
+        """The maximum-likelihood hyper-parameters of a binned model by EM on the cell masses, a
+        :class:`~isochrones_amd.binfit.BinnedFit`.  ``theta0``: one row to start from; default: uniform cell masses.  Every
+        step takes the expected counts of :meth:`cell_counts` and raises :meth:`lnlike`, which is evaluated after every step;
+        it stops when the rise is below ``tol`` nats or after ``max_iter`` steps.  A logit that leaves its ``logits`` range is
+        clipped and listed in ``on_bound``; the rise is promised only while none is.  ``errors``: the Laplace covariance of
+        the logits from :meth:`hessian` and the standard deviation of every cell's mass by the delta method.  Two independent
+        Histograms with an injection set, and a cell with expected stars that no detected injection covers, raise
+        ``ValueError``; so does a model without a Histogram."""
+        from . import binfit
+        return binfit.maximize(self, theta0, max_iter, tol, errors)
+
     def lnprior(self, theta):
         lp = self.model.lnprior(theta.detach().cpu().numpy() if dev.is_tensor(theta) else np.atleast_2d(theta))
         if dev.is_tensor(theta):
@@ -759,7 +792,8 @@ class PopulationPosterior:
     def fit_mcmc(self, nwalkers=64, nburn=200, niter=200, seed=None, p0=None):
         """Affine-invariant ensemble (framework-op :class:`~isochrones_amd.sampler.EnsembleSampler`) over the
         hyper-parameters; the walkers of a half-step are the H rows of one ``iso_hier_lnlike`` call.  ``p0`` [nwalkers, P];
-        default: drawn uniformly from the middle half of every free range."""
+        default: drawn uniformly from the middle half of every free range.
+        For a binned model ``maximize().theta`` is a good centre for ``p0``."""
         import torch
         from .sampler import EnsembleSampler
         P = self.model.n_params
