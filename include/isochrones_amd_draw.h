@@ -83,6 +83,8 @@ extern "C" {
 #define ISO_DRAW_MAX_BINS 64
 #define ISO_DRAW_NPAR 10
 #define ISO_DRAW_PHILOX_TAG 0xD7
+/* the grid's cap: workgroups of 256 lanes; a call of more than 256 * ISO_DRAW_MAX_BLOCKS systems strides */
+#define ISO_DRAW_MAX_BLOCKS 4096
 
 /* kinds: 1 .. 8 are the ISO_HIER_* values, 9 is ISO_RELATION_LINGAUSS */
 #define ISO_DRAW_FLAT 1

@@ -79,6 +79,8 @@ extern "C" {
 #define ISO_POPULATION_MAX_COLS 32
 #define ISO_POPULATION_MAX_BANDS 32
 #define ISO_POPULATION_MAX_COMPS 2
+/* the grid's cap: workgroups of 256 lanes; a call of more than 256 * ISO_POPULATION_MAX_BLOCKS systems strides */
+#define ISO_POPULATION_MAX_BLOCKS 2048
 
 /* every pointer is a device pointer the caller owns (a host pointer for iso_population_eval_host) */
 typedef struct iso_population_model_table {

@@ -93,6 +93,8 @@ extern "C" {
 #define ISO_PREDICT_MAX_COMPS 3
 #define ISO_PREDICT_NSPEC 4
 #define ISO_PREDICT_LANES 128
+/* the grid's cap: one workgroup an ensemble; a call of more than ISO_PREDICT_MAX_BLOCKS ensembles strides */
+#define ISO_PREDICT_MAX_BLOCKS 2048
 
 /* every pointer is a device pointer the caller owns (a host pointer for iso_predict_chain_host) */
 typedef struct iso_predict_model_table {

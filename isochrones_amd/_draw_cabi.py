@@ -15,6 +15,7 @@ MAX_COLS = 8
 MAX_BINS = 64
 NPAR = 10
 PHILOX_TAG = 0xD7
+MAX_BLOCKS = 4096
 FLAT, FLATLOG, POWERLAW, GAUSS, LOGNORMAL, CHABRIER, FEH, TRUNCGAUSS, LINGAUSS, TABLE, CONSTANT = range(1, 12)
 EXPORTED_SYMBOLS = ("iso_draw_version", "iso_draw_last_error", "iso_draw_systems", "iso_draw_systems_host",
                     "iso_draw_uniforms_host")

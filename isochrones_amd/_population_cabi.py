@@ -13,6 +13,7 @@ ERR_HIP = -2
 MAX_COLS = 32
 MAX_BANDS = 32
 MAX_COMPS = 2
+MAX_BLOCKS = 2048
 EXPORTED_SYMBOLS = ("iso_population_version", "iso_population_last_error", "iso_population_eval",
                     "iso_population_eval_host")
 

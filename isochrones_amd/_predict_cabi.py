@@ -13,6 +13,7 @@ MAX_BANDS = 32
 MAX_COMPS = 3
 NSPEC = 4
 LANES = 128
+MAX_BLOCKS = 2048
 EXPORTED_SYMBOLS = ("iso_predict_version", "iso_predict_last_error", "iso_predict_chain", "iso_predict_chain_host")
 
 

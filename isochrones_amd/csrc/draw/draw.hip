@@ -22,6 +22,7 @@
 namespace {
 
 constexpr int BLOCK = 256;                      // four wavefronts
+constexpr int MAX_BLOCKS = ISO_DRAW_MAX_BLOCKS; // 256 compute units, 16 workgroups each, the rest by striding
 constexpr int MAXC = ISO_DRAW_MAX_COLS;
 constexpr int MAXK = ISO_DRAW_MAX_BINS;
 constexpr double INV_ROOT2 = 0.7071067811865476;
@@ -364,7 +365,7 @@ int iso_draw_systems(const iso_draw_record* records, int32_t C, const int32_t* o
     K.first = (uint64_t)first;
     K.N = N;
     const int64_t want = (N + BLOCK - 1) / BLOCK;
-    const unsigned blocks = (unsigned)(want < 4096 ? want : 4096);      // 256 compute units, 16 workgroups each
+    const unsigned blocks = (unsigned)(want < MAX_BLOCKS ? want : MAX_BLOCKS);
     hipLaunchKernelGGL(k_draw_systems, dim3(blocks), dim3(BLOCK), 0, (hipStream_t)stream, K);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(ISO_DRAW_ERR_HIP, hipGetErrorString(e));

@@ -24,7 +24,7 @@
 namespace {
 
 constexpr int BLOCK = 256;
-constexpr int MAX_BLOCKS = 256 * 8;             // a gather-bound stream: eight workgroups per CU, the rest by striding
+constexpr int MAX_BLOCKS = ISO_POPULATION_MAX_BLOCKS;   // a gather-bound stream: eight workgroups per CU, the rest by striding
 constexpr int MAXC = ISO_POPULATION_MAX_COMPS;
 constexpr int GQ = 8;                           // model columns per pass
 constexpr int CH = 8;                           // bands per pass

@@ -23,7 +23,7 @@
 namespace {
 
 constexpr int BLOCK = ISO_PREDICT_LANES;
-constexpr int MAX_BLOCKS = 256 * 8;
+constexpr int MAX_BLOCKS = ISO_PREDICT_MAX_BLOCKS;      // eight workgroups per CU, the rest by striding
 constexpr int MAXC = ISO_PREDICT_MAX_COMPS;
 constexpr int CH = 8;                           // bands per pass
 constexpr int NSPEC = ISO_PREDICT_NSPEC;

@@ -10,6 +10,7 @@ inside."""
 import numpy as np
 
 from tests import _binned_twin as bt
+from tests._hier_twin import guarded, margins_untouched
 
 LD = np.longdouble
 LIMIT = 1e-11
@@ -183,10 +184,11 @@ def random_lnh(H, B, seed, zero=0.1):
 
 
 # -- the call ---------------------------------------------------------------------------------------------------------
-def call(lib, A, lnh, mask=None, device=None, pairs=True, rows=None):
+def call(lib, A, lnh, mask=None, device=None, pairs=True, rows=None, guard=False):
     """``iso_binfit_moments_host`` or, with ``device``, ``iso_binfit_moments`` on copies of the numpy inputs; ``rows``: a
     (first, count) sub-range of the rows of ``lnh``.  Returns ``(rc, dict)`` of numpy ``N``, ``C`` (the fill value -7 when
-    ``pairs`` is False), ``n_live``."""
+    ``pairs`` is False), ``n_live``.  With ``guard`` every device output lies between two margins of -7 that have to stay
+    so."""
     lnh = np.ascontiguousarray(lnh, dtype=np.float64)
     if rows is not None:
         lnh = np.ascontiguousarray(lnh[rows[0]:rows[0] + rows[1]])
@@ -196,6 +198,9 @@ def call(lib, A, lnh, mask=None, device=None, pairs=True, rows=None):
     dA, dl = up(A), up(lnh)
     dm = None if mask is None else up(np.ascontiguousarray(mask, dtype=np.int32))
     N, Cm, live = up(np.full((H, B), -7.0)), up(np.full((H, B, B), -7.0)), up(np.full(H, -7, np.int32))
+    flats = []
+    if guard and device is not None:
+        flats, (N, Cm, live) = zip(*[guarded(t.shape, t.dtype, device) for t in (N, Cm, live)])
     ws = None
     if device is not None:
         need = lib.iso_binfit_workspace_doubles(B, S, H, int(pairs))
@@ -205,4 +210,5 @@ def call(lib, A, lnh, mask=None, device=None, pairs=True, rows=None):
     if device is not None:
         import torch
         torch.cuda.synchronize()
+        assert all(margins_untouched(f) for f in flats), "a write outside an output"
     return rc, dict(N=host(N), C=host(Cm), n_live=host(live))

@@ -248,10 +248,27 @@ def special_cases():
 
 
 # -- the call ---------------------------------------------------------------------------------------------------------
-def call(lib, case, device=None, ens_begin=0, n_ens_out=None, rows=None, total=True, out=None):
+MARGIN = 64
+
+
+def guarded(shape, dtype, device):
+    """``(flat, view)``: a tensor of ``shape`` on ``device`` filled with -7, inside a buffer with MARGIN more of them either
+    side of it."""
+    import torch
+    n = int(np.prod(shape))
+    flat = torch.full((n + 2 * MARGIN,), -7, dtype=dtype, device=device)
+    return flat, flat[MARGIN:MARGIN + n].view(shape)
+
+
+def margins_untouched(flat):
+    return bool((flat[:MARGIN] == -7).all()) and bool((flat[-MARGIN:] == -7).all())
+
+
+def call(lib, case, device=None, ens_begin=0, n_ens_out=None, rows=None, total=True, out=None, guard=False):
     """``iso_hier_lnlike_host`` on the case's numpy storages or, with ``device`` (a torch device), ``iso_hier_lnlike`` on
     copies there.  Returns ``(rc, dict)`` of numpy arrays ``ell``, ``ess`` [H, S], ``n_bad`` [S], ``L``, ``min_ess`` [H];
-    what the call does not write keeps the fill value -7."""
+    what the call does not write keeps the fill value -7.  With ``guard`` every device output lies between two margins of
+    -7 that have to stay so."""
     S, W, T = case["S"], case["W"], case["T"]
     rows = case["rows"] if rows is None else rows
     H, Q = rows.shape
@@ -275,6 +292,9 @@ def call(lib, case, device=None, ens_begin=0, n_ens_out=None, rows=None, total=T
         ell, ess = torch.full((H, S), -7.0, **f64), torch.full((H, S), -7.0, **f64)
         n_bad = torch.full((S,), -7, dtype=torch.int32, device=device)
         L, mn = torch.full((H,), -7.0, **f64), torch.full((H,), -7.0, **f64)
+        flats = []
+        if guard:
+            flats, (ell, ess, n_bad, L, mn) = zip(*[guarded(t.shape, t.dtype, device) for t in (ell, ess, n_bad, L, mn)])
         interim = up(np.ascontiguousarray(case["interim"]).view(np.uint8))
         drows = up(np.ascontiguousarray(rows).view(np.uint8).reshape(-1))
         mask = None if mask is None else up(mask)
@@ -284,4 +304,6 @@ def call(lib, case, device=None, ens_begin=0, n_ens_out=None, rows=None, total=T
     rc = fn(cols, Q, case["layout"], T, S, W, ens_begin, n_ens_out, ptr(interim), ptr(drows), H, ptr(mask), ptr(ell),
             ptr(ess), ptr(n_bad), ptr(L if total else None), ptr(mn if total else None), stream)
     host = lambda a: a if isinstance(a, np.ndarray) else a.cpu().numpy()
+    if device is not None:
+        assert all(margins_untouched(f) for f in flats), "a write outside an output"
     return rc, dict(ell=host(ell), ess=host(ess), n_bad=host(n_bad), L=host(L), min_ess=host(mn))

@@ -237,6 +237,11 @@ def margins_untouched(flat):
 def device(dt, coords, dist, av, want=None, stream=None):
     """iso_population_eval on host arrays copied to the device -> dict of numpy outputs.  Every output lies between two
     margins of SENTINEL that have to stay so; an output not in ``want`` gets a null pointer."""
+    return {k: view.cpu().numpy() for k, view in device_tensors(dt, coords, dist, av, want, stream).items()}
+
+
+def device_tensors(dt, coords, dist, av, want=None, stream=None):
+    """:func:`device` with the outputs left on the device (a large batch is compared there, or on windows)."""
     import torch
     from isochrones_amd import _population_cabi as pc, device as dev
     Cn, _, N = coords.shape
@@ -249,7 +254,7 @@ def device(dt, coords, dist, av, want=None, stream=None):
     torch.cuda.synchronize()
     for k, (flat, _) in bufs.items():
         assert margins_untouched(flat), "the kernel wrote outside " + k
-    return {k: view.cpu().numpy() for k, (_, view) in bufs.items()}
+    return {k: view for k, (_, view) in bufs.items()}
 
 
 # ---- the Python layer without a device --------------------------------------------------------------------------------------

@@ -142,10 +142,11 @@ def want(case):
 
 
 # -- the call ---------------------------------------------------------------------------------------------------------
-def call(lib, case, device=None, rows=None, x_offset=0):
+def call(lib, case, device=None, rows=None, x_offset=0, guard=False):
     """``iso_select_alpha_host`` on the case's numpy arrays or, with ``device`` (a torch device), ``iso_select_alpha`` on
     copies there (``x_offset``: doubles of padding in front of x, so that it lies at another address).  Returns
-    ``(rc, dict)`` of numpy ``ln_alpha``, ``n_eff`` [H] and the int ``n_bad``; what the call does not write keeps -7."""
+    ``(rc, dict)`` of numpy ``ln_alpha``, ``n_eff`` [H] and the int ``n_bad``; what the call does not write keeps -7.  With
+    ``guard`` every device output lies between two margins of -7 that have to stay so."""
     rows = case["rows"] if rows is None else rows
     H, Q = rows.shape
     J = case["x"].shape[1]
@@ -166,9 +167,13 @@ def call(lib, case, device=None, rows=None, x_offset=0):
     ws = torch.full((int(lib.iso_select_workspace_doubles(J, H)),), float("nan"), **f64)
     la, ne = torch.full((H,), -7.0, **f64), torch.full((H,), -7.0, **f64)
     nb = torch.full((1,), -7, dtype=torch.int32, device=device)
+    flats = []
+    if guard:
+        flats, (la, ne, nb) = zip(*[ht.guarded(t.shape, t.dtype, device) for t in (la, ne, nb)])
     ptr = lambda a: C.c_void_p(a.data_ptr())
     rc = lib.iso_select_alpha(C.c_void_p(buf.data_ptr() + 8 * x_offset), Q, J, ptr(keep[0]), ptr(keep[1]), ptr(keep[2]), H,
                               ptr(ws), ptr(la), ptr(ne), ptr(nb), dev.stream_ptr(device.index))
+    assert all(ht.margins_untouched(f) for f in flats), "a write outside an output"
     return rc, dict(ln_alpha=la.cpu().numpy(), n_eff=ne.cpu().numpy(), n_bad=int(nb.cpu().numpy()[0]))
 
 

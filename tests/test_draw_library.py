@@ -57,7 +57,9 @@ def test_exports_exactly_the_bound_symbols():
     consts = dict(re.findall(r"#define ISO_DRAW_(\w+) (\S+)", body))
     assert int(consts["MAX_COLS"]) == dc.MAX_COLS == 8 and int(consts["MAX_BINS"]) == dc.MAX_BINS == 64
     assert int(consts["NPAR"]) == dc.NPAR and int(consts["PHILOX_TAG"], 16) == dc.PHILOX_TAG
-    assert dc.PHILOX_TAG not in (0x51, 0x4E)                         # the samplers' and the nested sampler's
+    assert int(consts["MAX_BLOCKS"]) == dc.MAX_BLOCKS == 4096
+    assert "constexpr int MAX_BLOCKS = ISO_DRAW_MAX_BLOCKS;" in open(B.sources()[0]).read()
+    assert dc.PHILOX_TAG not in (0x51, 0x4E)                        # the samplers' and the nested sampler's
     assert int(consts["ERR_INVALID"].strip("()")) == dc.ERR_INVALID and int(consts["ERR_HIP"].strip("()")) == dc.ERR_HIP
     kinds = ("FLAT", "FLATLOG", "POWERLAW", "GAUSS", "LOGNORMAL", "CHABRIER", "FEH", "TRUNCGAUSS", "LINGAUSS", "TABLE", "CONSTANT")
     assert [int(consts[k]) for k in kinds] == [getattr(dc, k) for k in kinds] == list(range(1, 12))

@@ -1,7 +1,7 @@
 """iso_binfit_moments (k_binfit_partial, k_binfit_total) on the device against iso_binfit_moments_host on the same tables:
 N and C within 1e-11 relative to max(1, n_live), n_live exact; S = 1, 255, 256, 257 (tiles of 64 stars and a ragged one),
-4096 and 4097 (a chunk and a second one); B = 1, 2, 63, 64, 3 x 5 and 8 x 8 cells; H = 1, 8, 9 rows; masked and dead stars,
-cells of height 0, no C; a row alone and in a batch, and a repeated call, bit for bit.  No table is larger than 4097 x 64
+4096 and 4097 (a chunk and a second one), 2 * 4096 + 1 and 3 * 4096 (a third, one of them without a live star); B = 1, 2, 63, 64, 3 x 5 and 8 x 8 cells; H = 1, 8, 9 rows; masked and dead stars,
+cells of height 0, no C; a row alone and in a batch, and a repeated call, bit for bit.  No table is larger than 12288 x 64
 doubles."""
 import numpy as np
 import pytest
@@ -34,8 +34,8 @@ def _case(S, B, H):
     return A, lnh, mask
 
 
-def _against_host(lib, device, A, lnh, mask, pairs=True):
-    rc, got = ft.call(lib, A, lnh, mask, device=device, pairs=pairs)
+def _against_host(lib, device, A, lnh, mask, pairs=True, guard=False):
+    rc, got = ft.call(lib, A, lnh, mask, device=device, pairs=pairs, guard=guard)
     assert rc == 0, lib.iso_binfit_last_error()
     rc, ref = ft.call(lib, A, lnh, mask, pairs=pairs)
     assert rc == 0
@@ -64,6 +64,26 @@ def test_device_matches_the_host_entry(lib, device, S, B, H):
     ft.assert_matches(got, A, lnh, mask)
     if S > 3:
         assert ref["n_live"].max() <= S - 6                             # three dead and three masked stars
+
+
+@pytest.mark.parametrize("S", [2 * fc.CHUNK + 1, 3 * fc.CHUNK])
+@pytest.mark.parametrize("B, H", [(64, 2), (15, 9)])
+def test_three_chunks_and_one_without_a_live_star(lib, device, S, B, H):
+    """nc = 3: the workspace index (h * nc + chunk) with a third chunk, ragged (one star) and full, and the totals over three
+    chunks.  The whole of chunk 1 is masked, so its partial sums are zeros and its live count is 0, between two chunks
+    that have dead and masked stars of their own."""
+    assert fc.CHUNK == 4096
+    A, lnh, mask = _case(S, B, H)
+    mask[fc.CHUNK:2 * fc.CHUNK] = 0
+    got, ref = _against_host(lib, device, A, lnh, mask, guard=True)
+    for k in ("N", "C", "n_live"):
+        assert not (got[k] == -7).any(), k
+    ft.assert_matches(got, A, lnh, mask)
+    assert 0 < ref["n_live"].min() and ref["n_live"].max() <= S - fc.CHUNK - 4
+    rc, one = ft.call(lib, A, lnh, mask, device=device, rows=(1, 1), guard=True)
+    assert rc == 0
+    for k in ("N", "C", "n_live"):
+        assert one[k].tobytes() == got[k][1:2].tobytes(), k
 
 
 @pytest.mark.parametrize("S, B, H", [(4097, 64, 9), (257, 15, 8), (1, 2, 1)])

@@ -1,7 +1,8 @@
 """iso_hier_lnlike (k_hier_stars, k_hier_total) on the device against iso_hier_lnlike_host, within the limits of
 tests/_hier_twin.py, on the smallest shapes at which the kernel can still go wrong: no full wavefront (M = 35), one
 wavefront exactly, several passes of a workgroup over its star (M = 1200), H = 1, the row tile, tile + 1 and 3 tiles + 5,
-Q = 1 and 4, both layouts, columns from two storages; every family kind; the -inf, NaN, masked and +-700 cases.  And bit
+Q = 1 and 4, both layouts, columns from two storages; S = 257 and 513 stars (more than the total's workgroup has threads);
+every family kind; the -inf, NaN, masked and +-700 cases.  And bit
 identity of a star's row alone, in a batch, in a sub-range of stars and in any tiling of the hyper rows."""
 import numpy as np
 import pytest
@@ -75,6 +76,37 @@ def test_special_cases(lib, device, name):
         assert np.isnan(g["ell"][:, 1]).all() and np.isnan(g["ess"][:, 1]).all() and g["n_bad"][1] == 0
     else:
         assert tw.want(case)["rmax"].max() > 690 and np.isfinite(g["ell"]).all() and np.isfinite(g["ess"]).all()
+
+
+BLOCK = 256                                                          # threads of k_hier_total's workgroup: a pass of row_total
+
+
+@pytest.mark.parametrize("S", [BLOCK + 1, 2 * BLOCK + 1])
+@pytest.mark.parametrize("masked", [False, True])
+def test_the_row_total_takes_a_second_and_a_third_pass_over_the_stars(lib, device, S, masked):
+    """More stars than the total's workgroup has threads: thread 0 adds a second star (S = 257) and a third (S = 513).
+    With the stars 0 .. 255 masked every term of L and min_ess comes from the second and the third pass."""
+    case = tw.random_case(S, 5, 7, 1, TILE + 1, seed=S)
+    keep = np.ones(S, bool)
+    if masked:
+        keep[:BLOCK] = False
+        case["mask"] = keep.astype(np.int32)
+    rc, host = tw.call(lib, case)
+    assert rc == 0, lib.iso_hier_last_error()
+    rc, got = tw.call(lib, case, device=device, guard=True)
+    assert rc == 0, lib.iso_hier_last_error()
+    for k in ("ell", "ess", "n_bad", "L", "min_ess"):
+        assert not (got[k] == -7).any(), k                           # (a masked star's ell and ess are written too: NaN)
+    twin = tw.want(case)
+    tw.assert_matches(host, twin, (S, masked, "host"))
+    tw.assert_matches(got, twin, (S, masked, "device"))
+    tw.assert_matches(got, dict(host, rmax=twin["rmax"]), (S, masked, "device against host"))
+    assert np.isfinite(got["L"]).all() and np.isnan(got["ell"][:, ~keep]).all() and np.isfinite(got["ell"][:, keep]).all()
+    # L and min_ess are the sum and the minimum of the device's own star terms
+    own = got["ell"][:, keep].sum(axis=1)
+    print("S = %d, masked %s: max |L - sum ell| / |sum ell| = %.2e" % (S, masked, np.max(np.abs(got["L"] - own) / np.abs(own))))
+    assert np.array_equal(got["min_ess"], got["ess"][:, keep].min(axis=1))
+    assert np.allclose(got["L"], own, rtol=1e-14, atol=0)
 
 
 @pytest.fixture(scope="module")

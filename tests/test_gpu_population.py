@@ -1,6 +1,6 @@
 """libiso_population.so on the device: the kernel against the host entry of the same library (model columns bit for bit,
 magnitudes and extinctions within 1e-9, identical NaN patterns) over the shapes at which the kernel takes another path,
-batch independence, no stray writes, a non-default stream; then the Python layer end to end against the independent path
+batch independence, no stray writes, a non-default stream, batches at and beyond the grid's cap; then the Python layer end to end against the independent path
 through ``interp_value`` / ``interp_mag`` (``ic.generate_binary``), the twin and the golden from the reference."""
 import ctypes as C
 import functools
@@ -78,6 +78,61 @@ def test_a_system_does_not_depend_on_its_batch():
     for k in tw.OUTPUTS:
         assert tw.margins_untouched(bufs[k][0]), k
         assert tw.same_bits(bufs[k][1].cpu().numpy(), full[k][..., lo:lo + n]), k
+
+
+BLOCK = 256                                                      # lanes of a workgroup
+
+
+def _cap():
+    from isochrones_amd import _population_cabi as pc
+    return pc.MAX_BLOCKS * BLOCK                                 # systems of one trip of the capped grid
+
+
+@pytest.mark.parametrize("trips", ("cap", "cap_plus_1", "two_caps_plus_65"))
+@pytest.mark.parametrize("Cn", (1, 2))
+@pytest.mark.parametrize("Q, B", ((4, 1), (18, 7)))
+def test_the_second_and_third_trip_of_the_stride_loop(Q, B, Cn, trips):
+    """N = CAP (every lane one system, the loop's exit test alone), CAP + 1 (lane 0 of workgroup 0 a second one) and
+    2 * CAP + 65 (a third trip of 65 lanes), CAP = ISO_POPULATION_MAX_BLOCKS * 256.
+
+    Compared with the host entry in full where that takes under a second for the 1.05e6 systems of 2 * CAP + 65 (measured
+    on one CPU core: Q = 4, B = 1 0.6 s single or binary, Q = 18, B = 7 single 0.9 s).  Q = 18, B = 7 binaries take it 2.6 s
+    and give 0.65 GB of outputs, so they are compared on three windows that contain every boundary between two trips:
+    [0, 513), [CAP - 256, CAP + 257) and the last 513 systems (clipped to the batch).  Everywhere: no sentinel is left in
+    an output (a system skipped), the margins are untouched (``device_tensors``), and the systems either side of the
+    first trip's end have the bits of a call on them alone."""
+    import torch
+    from isochrones_amd import _population_cabi as pc, device as dev
+    CAP = _cap()
+    assert pc.MAX_BLOCKS == 2048
+    N = {"cap": CAP, "cap_plus_1": CAP + 1, "two_caps_plus_65": 2 * CAP + 65}[trips]
+    dt, tab = _dt(Q, B), tw.tables(Q, B)
+    x, d, a = tw.inputs(N, Cn)
+    got = tw.device_tensors(dt, x, d, a)
+    for k in tw.OUTPUTS:
+        assert got[k].shape == tw.shapes(Cn, Q, B, N)[k] and not bool((got[k] == tw.SENTINEL).any()), k
+    if (Q, B, Cn) != (18, 7, 2):
+        windows = [(0, N)]
+    else:
+        windows = sorted({(0, 513), (CAP - 256, min(N, CAP + 257)), (N - 513, N)})
+    for lo, hi in windows:
+        want = tw.host(tab, np.ascontiguousarray(x[:, :, lo:hi]), d[lo:hi], a[lo:hi])
+        tw.assert_same({k: got[k][..., lo:hi].cpu().numpy() for k in tw.OUTPUTS}, want,
+                       "Q=%d B=%d C=%d N=%d [%d, %d)" % (Q, B, Cn, N, lo, hi))
+    # a call on the sub-range alone: distance and AV are pointers into the larger arrays, the coordinates its packed rows
+    lo, hi = CAP - 64, min(N, CAP + 65)
+    n = hi - lo
+    up = lambda v: torch.as_tensor(np.ascontiguousarray(v), device="cuda")      # noqa: E731
+    d_x, d_d, d_a = up(x[:, :, lo:hi]), up(d), up(a)
+    bufs = {k: tw.guarded(s) for k, s in tw.shapes(Cn, Q, B, n).items()}
+    out = pc.IsoPopulationOut(*[dev.ptr(bufs[k][1]) for k in tw.OUTPUTS])
+    pc.check(pc.lib().iso_population_eval(C.byref(dt.model), C.byref(dt.bct), dev.ptr(d_x), d_d.data_ptr() + 8 * lo,
+                                          d_a.data_ptr() + 8 * lo, n, Cn, C.byref(out), dev.stream_ptr(0)))
+    torch.cuda.synchronize()
+    for k in tw.OUTPUTS:
+        assert tw.margins_untouched(bufs[k][0]), k
+        # (as 64-bit patterns: the NaNs of an off-grid system are the same bits too)
+        assert torch.equal(bufs[k][1].view(torch.int64), got[k][..., lo:hi].contiguous().view(torch.int64)), k
 
 
 def test_null_outputs_stay_unwritten_and_margins_untouched():

@@ -1,5 +1,6 @@
 """iso_predict_chain on the GPU against iso_predict_chain_host, the numpy twin and the C oracle; bit identity of a star's
-outputs alone, in a batch, in a range and from either layout; edge cases the twin alone fixes; the Python surface.
+outputs alone, in a batch, in a range and from either layout; more stars than the grid has workgroups; edge cases the twin
+alone fixes; the Python surface.
 
 Tolerances (the issue's): magnitudes within 1e-9 (1 + |b|) of the oracle, term_chi2 and ppc within rtol 1e-9 of the
 long-double twin, n_bad / map_index / map_pars exact."""
@@ -79,6 +80,82 @@ def test_a_star_has_the_same_bits_alone_in_a_batch_in_a_range_and_from_either_la
         one = full[k][:, :, sl] if k == "mags" else full[k][e:e + 1]
         assert tw.same_bits(rng[k][:, :, :W] if k == "mags" else rng[k][:1], one), k
         assert tw.same_bits(alone[k], one), k
+
+
+def _check_against_host(got, hst, what):
+    """every output of every star against the host entry, and no fill value left where the kernel has to write"""
+    for k in got:
+        assert not (got[k] == -7).any(), (what, k)
+    assert tw.mags_close(got["mags"], hst["mags"])[0], what
+    for k in ("term_chi2", "ppc"):
+        ok, dev_ = tw.rel_close(got[k], hst[k])
+        assert ok, (what, k, dev_)
+    for k in ("n_bad", "map_index", "mag_nan"):
+        np.testing.assert_array_equal(got[k], hst[k], err_msg="%s %s" % (what, k))
+    assert tw.same_bits(got["map_pars"], hst["map_pars"]), what
+
+
+def test_a_workgroup_takes_a_second_and_a_third_star():
+    """S = 2 * ISO_PREDICT_MAX_BLOCKS + 1 stars of six samples (fewer than lanes): workgroup 0 takes the stars 0, 2 048 and
+    4 096 in turn and reuses its LDS (the partial sums, the sample in flight, the bad and the NaN counts, the MAP tree).  What
+    the first star leaves there would show in the second, the second's in the third: star 0 has every sample bad (n_bad = n,
+    every mag_nan count full), star 2 048 is clean, star 4 096 lacks observations in some bands and has no finite lnprob
+    (map_index = -1).  Then the same storage extended by five stars, read from star 3 on: the stars 3, 2 051 and 4 099
+    carry the same three states."""
+    from isochrones_amd import _predict_cabi as pc
+    kind, B, Cn, W, T = "iso", 9, 2, 2, 3
+    S = 2 * pc.MAX_BLOCKS + 1
+    assert pc.MAX_BLOCKS == 2048 and W * T < pc.LANES
+    tab = tw.tables(kind, B)
+    _, ax3, _, _ = tab
+    comps, i_dist, i_AV = tw.comps_for(Cn)
+    x, lp = (v.copy() for v in tw.chain(kind, S + 5, W, T, Cn))
+    val, unc = tw.observations(kind, S + 5, B)
+    rng = np.random.default_rng(3)
+    bad, clean, holes = (0, 3), (pc.MAX_BLOCKS, pc.MAX_BLOCKS + 3), (2 * pc.MAX_BLOCKS, 2 * pc.MAX_BLOCKS + 3)
+    for s in bad + clean + holes:
+        sl = slice(s * W, (s + 1) * W)
+        x[:, 0:Cn, sl] = rng.uniform(250.0, 400.0, (T, Cn, W))                 # on both grids to begin with
+        x[:, Cn, sl] = 0.5 * (ax3[0][0] + ax3[0][-1]) + rng.uniform(-0.05, 0.05, (T, W))
+        x[:, Cn + 1, sl] = 0.5 * (ax3[1][0] + ax3[1][-1]) + rng.uniform(-0.05, 0.05, (T, W))
+        x[:, i_dist, sl] = rng.uniform(150.0, 250.0, (T, W))
+        x[:, i_AV, sl] = rng.uniform(0.1, 0.3, (T, W))
+        val[s] = np.where(np.isnan(val[s]), 9.0, val[s])
+    for s in bad:
+        x[:, i_dist, s * W:(s + 1) * W] = np.nan
+    for s in holes:
+        val[s, [1, 4, B - 1, B + 2]] = np.nan
+        lp[:, s * W:(s + 1) * W] = np.nan
+    first = np.ascontiguousarray(x[:, :, :S * W]), np.ascontiguousarray(lp[:, :S * W])
+    got = tw.device(tab, first[0], first[1], tw.PARAM_MAJOR, S, W, comps, i_dist, i_AV, val[:S], unc[:S])
+    hst = tw.host(tab, first[0], first[1], tw.PARAM_MAJOR, S, W, comps, i_dist, i_AV, val[:S], unc[:S])
+    _check_against_host(got, hst, "S = %d" % S)
+    n = W * T
+    assert got["n_bad"][bad[0]] == n and (got["mag_nan"][bad[0]] == n).all() and np.isnan(got["ppc"][bad[0]])
+    assert got["n_bad"][clean[0]] == 0 and (got["mag_nan"][clean[0]] == 0).all() and np.isfinite(got["ppc"][clean[0]])
+    assert np.isfinite(got["term_chi2"][clean[0]]).all() and 0 <= got["map_index"][clean[0]] < n
+    assert got["map_index"][holes[0]] == -1 and np.isnan(got["map_pars"][holes[0]]).all() and got["n_bad"][holes[0]] == 0
+    assert np.array_equal(np.isnan(got["term_chi2"][holes[0]]), np.isnan(val[holes[0]])) and np.isfinite(got["ppc"][holes[0]])
+    # the stars around every change of star of workgroup 0, against the long-double twin
+    stars = np.array([0, 1, pc.MAX_BLOCKS - 1, pc.MAX_BLOCKS, pc.MAX_BLOCKS + 1, 2 * pc.MAX_BLOCKS - 1, 2 * pc.MAX_BLOCKS])
+    cols = (stars[:, None] * W + np.arange(W)).ravel()
+    want = tw.predict(tab, np.ascontiguousarray(x[:, :, cols]), np.ascontiguousarray(lp[:, cols]), tw.PARAM_MAJOR, len(stars), W,
+                      comps, i_dist, i_AV, val[stars], unc[stars])
+    assert tw.mags_close(got["mags"][:, :, cols], want["mags"])[0]
+    for k in ("term_chi2", "ppc"):
+        ok, dev_ = tw.rel_close(got[k][stars], want[k])
+        assert ok, (k, dev_)
+    for k in ("n_bad", "map_index", "mag_nan"):
+        np.testing.assert_array_equal(got[k][stars], want[k], err_msg=k)
+    assert tw.same_bits(got["map_pars"][stars], want["map_pars"])
+    # n_ens = S + 5, ens_begin = 3, n_ens_out = S
+    rng_ = tw.device(tab, x, lp, tw.PARAM_MAJOR, S + 5, W, comps, i_dist, i_AV, val, unc, ens_begin=3, n_out=S)
+    hst = tw.host(tab, x, lp, tw.PARAM_MAJOR, S + 5, W, comps, i_dist, i_AV, val, unc, ens_begin=3, n_out=S)
+    _check_against_host(rng_, hst, "S = %d from star 3" % S)
+    assert rng_["n_bad"][0] == n and rng_["n_bad"][pc.MAX_BLOCKS] == 0 and rng_["map_index"][2 * pc.MAX_BLOCKS] == -1
+    for k in ("term_chi2", "ppc", "n_bad", "map_index", "map_pars", "mag_nan"):     # a star's bits do not depend on its workgroup
+        assert tw.same_bits(rng_[k][:S - 3], got[k][3:]), k
+    assert tw.same_bits(rng_["mags"][:, :, :(S - 3) * W], got["mags"][:, :, 3 * W:])
 
 
 def test_edge_cases_fixed_by_the_twin():

@@ -1,7 +1,7 @@
 """iso_relation_lnlike (k_relation_stars, k_relation_total) on the device against iso_relation_lnlike_host and the twin of
 tests/_relation_twin.py, on test_gpu_hier.py's shapes (M = 35, 64 and 1200; H = 1, the row tile, tile + 1 and 3 tiles + 5;
 both layouts) with one link, a chain of links, a parent above its child, parent and child in two storages; the NaN, -inf,
-masked and +-700 cases; slope 0 against iso_hier_lnlike's TRUNCGAUSS.  And bit identity: records of the kinds 1 .. 8 give
+masked and +-700 cases; 257 and 513 stars (more than the total's workgroup has threads); slope 0 against iso_hier_lnlike's TRUNCGAUSS.  And bit identity: records of the kinds 1 .. 8 give
 iso_hier_lnlike's bits; a star alone, in a batch and in a sub-range, a row alone and in any tiling, a repeated call and
 another storage and layout give the same bits."""
 import numpy as np
@@ -53,6 +53,37 @@ def test_device_matches_the_host_entry_and_the_twin(lib, device, S, W, T, Q, H, 
 def test_special_cases(lib, device, name):
     case = rt.special_cases()[name]
     rt.check_special(name, case, _against_host(lib, device, case, name))
+
+
+BLOCK = 256                                                          # threads of k_relation_total's workgroup: a pass of row_total
+
+
+@pytest.mark.parametrize("S", [BLOCK + 1, 2 * BLOCK + 1])
+@pytest.mark.parametrize("masked", [False, True])
+def test_the_row_total_takes_a_second_and_a_third_pass_over_the_stars(lib, device, S, masked):
+    """More stars than the total's workgroup has threads: thread 0 adds a second star (S = 257) and a third (S = 513).
+    With the stars 0 .. 255 masked every term of L and min_ess comes from the second and the third pass."""
+    case = rt.linked_case(S, 5, 7, 2, TILE + 1, seed=S, links={1: 0})
+    keep = np.ones(S, bool)
+    if masked:
+        keep[:BLOCK] = False
+        case["mask"] = keep.astype(np.int32)
+    rc, host = rt.call(lib, case)
+    assert rc == 0, lib.iso_relation_last_error()
+    rc, got = rt.call(lib, case, device=device, guard=True)
+    assert rc == 0, lib.iso_relation_last_error()
+    for k in ("ell", "ess", "n_bad", "L", "min_ess"):
+        assert not (got[k] == -7).any(), k                           # (a masked star's ell and ess are written too: NaN)
+    twin = rt.want(case)
+    rt.assert_matches(host, twin, (S, masked, "host"))
+    rt.assert_matches(got, twin, (S, masked, "device"))
+    rt.assert_matches(got, dict(host, rmax=twin["rmax"]), (S, masked, "device against host"))
+    assert np.isfinite(got["L"]).all() and np.isnan(got["ell"][:, ~keep]).all() and np.isfinite(got["ell"][:, keep]).all()
+    # L and min_ess are the sum and the minimum of the device's own star terms
+    own = got["ell"][:, keep].sum(axis=1)
+    print("S = %d, masked %s: max |L - sum ell| / |sum ell| = %.2e" % (S, masked, np.max(np.abs(got["L"] - own) / np.abs(own))))
+    assert np.array_equal(got["min_ess"], got["ess"][:, keep].min(axis=1))
+    assert np.allclose(got["L"], own, rtol=1e-14, atol=0)
 
 
 def test_a_linked_interim_record_is_nan_on_the_device(lib, device):

@@ -1,7 +1,8 @@
 """iso_select_alpha (k_select_partial, k_select_total) on the device against iso_select_alpha_host and the long-double
 twin, within the limits of tests/_select_twin.py, on the smallest shapes at which the kernels can still go wrong: no full
 wavefront (J = 1, 37), one pass of the workgroup exactly (256) and a partial second one (257), one chunk short by one
-(4095), one chunk exactly (4096), two chunks (4097) and four with a ragged last one (3 * 4096 + 5); H = 1, the row tile,
+(4095), one chunk exactly (4096), two chunks (4097) and four with a ragged last one (3 * 4096 + 5), 65 and 257 chunks (a
+second wavefront and a second pass of the total); H = 1, the row tile,
 tile + 1 and 3 tiles + 5; Q = 1 and 4; every family kind; the -inf, NaN, zero-density and +-700 cases.  And bit identity
 of a row alone, in any range or tiling of the rows, on a repeated call and from x at another address."""
 import numpy as np
@@ -80,6 +81,76 @@ def test_a_chunk_without_support_next_to_one_with(lib, device):
     case["x"][1, 2 * CHUNK:] = np.nan
     got = _against_host(lib, device, case, "empty chunk")
     assert got["n_bad"] == 100 and np.isfinite(got["ln_alpha"]).all()
+
+
+BLOCK = 256                                                         # threads of k_select_total's workgroup
+
+
+def many_chunks_case(C, Q, H, bad_tail):
+    """J = (C - 1) * CHUNK + 1 injections in C chunks, the last chunk the one injection J - 1.  Flat draws, Gaussian rows
+    whose means and widths differ a little, so that r is largest near x = 0 under every row: injection J - 1 sits there
+    with lnd = 0 and every other one has lnd <= -12, so it carries the largest term r + lnd of every row and a weight of
+    the order of all the others' together.  A whole chunk in the middle and the injection J - 2 are undetected
+    (lnd = -inf); an injection of chunk 0 and one of chunk 64 (where that is not the last) have a NaN x.  With ``bad_tail``
+    injection J - 1 has a NaN x instead: the last chunk is without support, and its bad count is the last term of n_bad.
+    Returns ``(case, n_bad)``."""
+    from isochrones_amd import priors as P
+    J = (C - 1) * CHUNK + 1
+    rng = np.random.default_rng(C + Q + H)
+    x = rng.uniform(-3.5, 3.5, (Q, J))
+    x[:, J - 1] = 0.0
+    lnd = tw._lnd(rng, J) - 12.0
+    lnd[J - 1] = 0.0
+    mid = C // 2
+    lnd[mid * CHUNK:(mid + 1) * CHUNK] = -np.inf
+    lnd[J - 2] = -np.inf
+    nan_at = [(0, 5)] + ([(Q - 1, 64 * CHUNK + 7)] if C > 65 else []) + ([(0, J - 1)] if bad_tail else [])
+    for q, j in nan_at:
+        x[q, j] = np.nan
+    mu, sg = rng.uniform(-0.2, 0.2, (H, Q)), rng.uniform(0.8, 1.2, (H, Q))
+    case = tw.fixed_case(x, lnd, [P.FlatPrior((-4.0, 4.0))] * Q,
+                         [[P.GaussianPrior(mu[h, q], sg[h, q]) for q in range(Q)] for h in range(H)])
+    if not bad_tail:                                                # the largest term of every row is the last chunk's
+        with np.errstate(invalid="ignore"):
+            t = sum(-0.5 * ((x[q][None] - mu[:, q, None]) / sg[:, q, None]) ** 2 for q in range(Q)) + lnd[None]
+        assert (np.nanmax(t[:, :J - 1], axis=1) < t[:, J - 1] - 11.0).all()
+    return case, len(nan_at)
+
+
+@pytest.mark.parametrize("bad_tail", [False, True])
+@pytest.mark.parametrize("C, Q, H", [(BLOCK // 4 + 1, 4, 1), (BLOCK + 1, 1, TILE + 1)])
+def test_the_total_over_more_chunks_than_a_wavefront_and_than_the_workgroup(lib, device, C, Q, H, bad_tail):
+    """C = 65 chunks: the second wavefront of k_select_total has work.  C = 257: thread 0 takes a second chunk in each of
+    the total's three loops (the maximum, the two sums, the bad counts).  Without the last chunk ln_alpha is off in
+    its first decimal place, against a limit of 1e-11."""
+    case, n_bad = many_chunks_case(C, Q, H, bad_tail)
+    assert case["x"].shape == (Q, (C - 1) * CHUNK + 1)
+    rc, host = tw.call(lib, case)
+    assert rc == 0, lib.iso_select_last_error()
+    rc, got = tw.call(lib, case, device=device, guard=True)
+    assert rc == 0, lib.iso_select_last_error()
+    assert not (got["ln_alpha"] == -7.0).any() and not (got["n_eff"] == -7.0).any()
+    assert got["n_bad"] == host["n_bad"] == n_bad
+    twin = tw.want(case)
+    fin = np.isfinite(twin["ln_alpha"])
+    assert fin.all()
+    for name, res in (("host", host), ("device", got)):
+        print("C = %d, Q = %d, H = %d, bad tail %s: %s against the twin, max |d ln_alpha| = %.2e, max |d n_eff| / n_eff = %.2e"
+              % (C, Q, H, bad_tail, name, np.max(np.abs(res["ln_alpha"] - twin["ln_alpha"])),
+                 np.max(np.abs(res["n_eff"] - twin["n_eff"]) / twin["n_eff"])))
+    tw.assert_matches(got, twin, (C, "device"))
+    tw.assert_matches(host, twin, (C, "host"))
+    tw.assert_matches(got, dict(host, tmax=twin["tmax"]), (C, "device against host"))
+    if bad_tail:
+        return
+    # the last injection weighs as much as the rest: far fewer effective injections than detected ones
+    assert (got["n_eff"] < 1e-3 * case["x"].shape[1]).all()
+    rc, again = tw.call(lib, case, device=device, guard=True)
+    assert rc == 0 and all(again[k].tobytes() == got[k].tobytes() for k in ("ln_alpha", "n_eff")) and again["n_bad"] == n_bad
+    if H > TILE:
+        rc, one = tw.call(lib, case, device=device, rows=case["rows"][TILE:TILE + 1], guard=True)
+        assert rc == 0 and one["n_bad"] == n_bad
+        assert one["ln_alpha"].tobytes() == got["ln_alpha"][TILE:].tobytes() and one["n_eff"].tobytes() == got["n_eff"][TILE:].tobytes()
 
 
 @pytest.fixture(scope="module")

@@ -42,6 +42,8 @@ def test_exports_exactly_the_bound_symbols():
     consts = dict(re.findall(r"#define ISO_POPULATION_(\w+) (\S+)", text))
     assert int(consts["MAX_COLS"]) == pc.MAX_COLS == 32 and int(consts["MAX_BANDS"]) == pc.MAX_BANDS == 32
     assert int(consts["MAX_COMPS"]) == pc.MAX_COMPS == 2
+    assert int(consts["MAX_BLOCKS"]) == pc.MAX_BLOCKS == 2048
+    assert "constexpr int MAX_BLOCKS = ISO_POPULATION_MAX_BLOCKS;" in open(os.path.join(B.SRC, "population.hip")).read()
     assert int(consts["ERR_INVALID"].strip("()")) == pc.ERR_INVALID
     assert int(consts["ERR_HIP"].strip("()")) == pc.ERR_HIP
     assert ctypes.sizeof(pc.IsoPopulationModelTable) == 4 * 8 + 8 * 4

@@ -38,6 +38,8 @@ def test_exports_exactly_the_bound_symbols():
     assert int(consts["PARAM_MAJOR"]) == _cabi.CHAIN_PARAM_MAJOR and int(consts["ROW_MAJOR"]) == _cabi.CHAIN_ROW_MAJOR
     assert int(consts["MAX_BANDS"]) == _predict_cabi.MAX_BANDS == 32 and int(consts["MAX_COMPS"]) == _predict_cabi.MAX_COMPS
     assert int(consts["LANES"]) == _predict_cabi.LANES and int(consts["NSPEC"]) == _predict_cabi.NSPEC
+    assert int(consts["MAX_BLOCKS"]) == _predict_cabi.MAX_BLOCKS == 2048
+    assert "constexpr int MAX_BLOCKS = ISO_PREDICT_MAX_BLOCKS;" in open(os.path.join(B.SRC, "predict.hip")).read()
     assert int(consts["ERR_INVALID"].strip("()")) == _predict_cabi.ERR_INVALID
     assert int(consts["ERR_HIP"].strip("()")) == _predict_cabi.ERR_HIP
     assert ctypes.sizeof(_predict_cabi.IsoPredictModelTable) == 4 * 8 + 4 * 4
