@@ -36,5 +36,7 @@ from . import draws
 from .draws import DrawPlan
 from . import binfit
 from .binfit import BinnedFit
+from . import emfit
+from .emfit import BinnedBootstrap
 
 __version__ = "0.1.0"

@@ -275,6 +275,32 @@ BINFIT = KernelLibrary(
     max_vgpr=128, min_waves=4,
     extra_headers=("../../include/isochrones_amd_binned.h", "../../include/isochrones_amd_hier.h", "common/last_error.h"))
 
+# a batch of weighted EM fits of a binned population's cell masses, and the star weights of a bootstrap (csrc/emfit/): one
+# workgroup per replicate iterates masses <- N / sum N on BINNED's per-star tables with the whole loop inside the kernel, so
+# R bootstrap replicates cost no host round trip per step.  It reads no record and no chain; its header includes BINNED's for
+# the limit of a grid, and the weights come from common/philox.h
+# -ffp-contract=off: the compiler fuses nothing, and the sources write no fma(): every product and every sum of the header's
+# definition is rounded on its own (a replicate's outputs are bit-identical alone, in any batch, at any replicate offset, in
+# any chain of launches and on every call)
+EMFIT = KernelLibrary(
+    name="emfit", flags=_NO_CONTRACT,
+    #: every kernel the library compiles (tests/test_emfit_library.py pins this set)
+    kernels=("k_emfit_run<8>", "k_emfit_run<16>", "k_emfit_run<32>", "k_emfit_run<64>", "k_emfit_weights"),
+    #: k_emfit_run<64> compiles to 208 VGPRs, no scratch, no spill, 3.7 KB of LDS and 2 waves per SIMD; <32> to 144 (3 waves),
+    #: <16> to 110 and <8> to 100 (4).  A lane holds one sum per cell of the padded grid (2 BP registers: 128 at 64 cells), the
+    #: star's Q, W and live sums, the eight loads a pass has in flight with their addresses, and an inlined log and division.
+    #: Left alone the compiler lifts the BP heights of the second pass and the BP comparisons with B out of the star loop
+    #: (254 VGPRs, 260 B of scratch and 107 spilled SGPRs at 64 cells): above 16 cells the heights are read from LDS per
+    #: star, as in the first pass, and B is compared as a scalar where it is used.  With one load waited for at a time
+    #: the second pass was the kernel's latency (192 VGPRs, 519 us an evaluation of 10^4 stars x 64 cells); eight a group
+    #: cost 16 registers and took it to 230 us.  One workgroup runs a replicate whatever its occupancy and a batch of R
+    #: replicates fills R CUs, so the second wave per SIMD only hides the loads of another replicate on the same CU
+    #: (R > 256); the budget is the 2-waves-per-SIMD one: 256 VGPRs, and no scratch at all.  k_emfit_weights (ten Philox
+    #: rounds, eighteen comparisons or one log) is 19 VGPRs at 8 waves
+    max_vgpr=256, min_waves=2,
+    extra_headers=("../../include/isochrones_amd_binned.h", "../../include/isochrones_amd_hier.h", "common/last_error.h",
+                   "common/philox.h", "common/wave_reduce.h"))
+
 #: the six libraries the shared builder started with (tests/test_side_libraries_cpu.py pins this tuple to exactly these)
 ALL = (CLUSTER, NESTED, SOLVE, DIAG, DERIVED, PREDICT)
 #: what __graft_entry__.build() and the command line below build, in order: ALL and the libraries added since ALL was
@@ -289,8 +315,9 @@ ADDED = (HIER,)
 NEWER = (SELECT, REWEIGHT, RELATION, BINNED)
 #: the libraries added after NEWER was pinned in its turn (tests/test_side_libraries_cpu.py names its members);
 #: __graft_entry__.build() and the command line below go through BUILD_ORDER + ADDED + NEWER + LATEST.  The next library goes
-#: here: tests/test_shrink_library.py asserts membership, not equality, so this tuple grows
-LATEST = (SHRINK, DRAW, BINFIT)
+#: here: tests/test_shrink_library.py asserts membership, not equality, so this tuple grows (tests/test_emfit_library.py pins
+#: EMFIT as its fourth member)
+LATEST = (SHRINK, DRAW, BINFIT, EMFIT)
 
 
 if __name__ == "__main__":

@@ -762,6 +762,30 @@ class PopulationPosterior:
         from . import binfit
         return binfit.maximize(self, theta0, max_iter, tol, errors)
 
+    # -- bootstrap errors for a binned model (isochrones_amd.emfit; the kernels of libiso_emfit.so) -------------------------
+    def em_masses(self, weights=None, g0=None, max_iter=2000, tol=1e-8):
+        """A batch of weighted EM fits of a binned model's cell masses on the per-star tables, the whole iteration in one
+        kernel where the chain lies (``iso_emfit_run``): numpy ``(g [R, B], objective [R], n_iter [R], status [R], n_live
+        [R])``.  ``weights`` [R, S]: a weight per replicate and star, default one replicate of ones; ``g0`` [B] or [R, B]:
+        the start masses, default uniform cell masses.  A replicate stops when its weighted log likelihood rises by less than
+        ``tol`` or after ``max_iter`` steps (``status``: ``isochrones_amd.emfit.STATUS_NAMES``).  With an injection set ``g``
+        is the distribution of the detected stars, ``h_b a_b / alpha``; a cell that no detected injection covers and that
+        holds expected stars raises :meth:`maximize`'s ``ValueError``.  A model without a Histogram, or with two independent
+        ones, raises ``ValueError``."""
+        from . import emfit
+        return emfit.em_masses(self, weights, g0, max_iter, tol)
+
+    def bootstrap(self, theta0=None, n_boot=200, seed=0, weights="poisson", q=(0.16, 0.5, 0.84), max_iter=2000, tol=1e-8):
+        """Bootstrap errors of the maximum-likelihood cell masses of a binned model, a
+        :class:`~isochrones_amd.emfit.BinnedBootstrap`: ``n_boot`` fits under resampled star weights next to the unweighted
+        fit (replicate 0), all in one batch of :meth:`em_masses` from ``theta0`` (default: uniform cell masses).
+        ``weights``: "poisson" (Poisson(1) counts, the bootstrap of the stars), "bayesian" (exponential weights) or an
+        array [R, S]; ``seed`` fixes them.  The errors hold where a cell's mass is 0, where :meth:`maximize`'s Laplace
+        covariance is NaN.  ``n_boot < 2``, a model without a Histogram and two independent Histograms raise
+        ``ValueError``."""
+        from . import emfit
+        return emfit.bootstrap(self, theta0, n_boot, seed, weights, q, max_iter, tol)
+
     def lnprior(self, theta):
         lp = self.model.lnprior(theta.detach().cpu().numpy() if dev.is_tensor(theta) else np.atleast_2d(theta))
         if dev.is_tensor(theta):
