@@ -246,8 +246,11 @@ def _column(spec):
     from .hierarchical import _Family
     if isinstance(spec, Column):
         return spec
-    if isinstance(spec, _p.DEVICE_PRIOR_TYPES):
+    if not _p.is_host_prior(spec):
         return prior_column(spec)
+    if isinstance(spec, _p.DEVICE_PRIOR_TYPES):      # a subclass with a density of its own: its sample() is the parent's
+        raise TypeError("a column of a DrawPlan is a device prior, a bound family, a float, a scipy uniform or an object "
+                        "with sample / rvs (got %r, which overrides its family's density)" % (spec,))
     if isinstance(spec, _Family):
         return bound(spec)
     if isinstance(spec, tuple) and len(spec) == 2 and isinstance(spec[0], _Family):

@@ -7,7 +7,8 @@ per-model *constants* (bounds, normalisations) and packs them into ``iso_prior``
 same.  The families the reference ships (its ``BasicStarModel`` defaults plus the simple bounded
 ones) are evaluated on the device.  Any OTHER ``Prior`` object — a user's subclass that defines
 ``_pdf`` (and optionally ``_lnpdf`` / ``distribution``) the way the reference's base class expects
-(priors.py:31-73) — is a *host prior*: the device sees a flat stand-in over its bounds and the model
+(priors.py:31-73), or a subclass of a device family that overrides what decides its density
+(``DENSITY_HOOKS``) — is a *host prior*: the device sees a flat stand-in over its bounds and the model
 adds ``lnpdf`` of that parameter on the host (``starmodel._HostPriorMixin``); such a model is fitted
 by the framework-op sampler, not by the resident kernels.
 
@@ -42,6 +43,52 @@ def _ncdf(z):
 EPOCH = [0]
 
 
+#: what decides a prior's density: a user's subclass of a device family that defines one of these is evaluated on the
+#: host (:func:`is_host_prior`) - the device would evaluate the parent's record
+DENSITY_HOOKS = ("_pdf", "pdf", "__call__", "_lnpdf", "lnpdf", "_raw", "_raw_array", "pdf_array", "lnpdf_array", "kind",
+                 "bounded")
+
+
+def _user_classes(cls):
+    """The classes of ``cls.__mro__`` in front of the first one this module defines."""
+    out = []
+    for k in cls.__mro__:
+        if k.__module__ == __name__:
+            break
+        out.append(k)
+    return out
+
+
+def _user_pdf(self, x):
+    # the reference's Prior.pdf (priors.py:54-59): bounds test, then the subclass's _pdf over _norm
+    lo, hi = self.bounds
+    if x < lo or x > hi:
+        return 0.0
+    return self._pdf(x) / getattr(self, "_norm", 1.0)
+
+
+def _user_pdf_array(self, x):
+    x = np.asarray(x, dtype=float)
+    with np.errstate(all="ignore"):
+        return np.array([self.pdf(float(v)) for v in x.ravel()], dtype=float).reshape(x.shape)
+
+
+def _user_lnpdf_own(self, x):
+    # the reference's lnpdf with a _lnpdf hook (priors.py:61-63; BoundedPrior puts its bounds test in front, :131-137)
+    if self._ref_bounded:
+        lo, hi = self.bounds
+        if x < lo or x > hi:
+            return -np.inf
+    return self._lnpdf(x)
+
+
+def _user_lnpdf_from_pdf(self, x):
+    # ... and without one (priors.py:64-66, :138-140): the log of pdf, which has the bounds test
+    p = self.pdf(x)
+    with np.errstate(all="ignore"):
+        return float(np.log(p)) if p else -np.inf
+
+
 class Prior:
     """Common surface: ``bounds``, ``pdf(x)``, ``lnpdf(x)``, ``__call__`` (= pdf), ``desc()``."""
 
@@ -49,6 +96,29 @@ class Prior:
     bounded = 0
     _bounds = (-np.inf, np.inf)
     _version = 0          # bumped on every mutation: models sharing a prior object notice (starmodel._prior_state)
+    _ref_bounded = False  # the reference derives this family from BoundedPrior: lnpdf tests the bounds before _lnpdf
+    _ref_has_lnpdf = False  # the reference's class of this family has a _lnpdf of its own
+
+    def __init_subclass__(cls, **kwargs):
+        """A user's subclass of a DEVICE family that writes the reference's hooks ``_pdf`` / ``_lnpdf`` gets the reference's
+        resolution order (priors.py:54-67, 131-140) - this package's families answer ``pdf`` / ``lnpdf`` from closed forms
+        that never look at those hooks.  Done once, when the class is made; the package's own classes and subclasses of the
+        base class (which already resolves that way) are left alone."""
+        super().__init_subclass__(**kwargs)
+        if cls.__module__ == __name__ or cls.kind == 0:
+            return
+        own = {}
+        for k in reversed(_user_classes(cls)):
+            own.update(k.__dict__)
+        if "_pdf" in own:
+            for name, fn in (("pdf", _user_pdf), ("__call__", _user_pdf), ("pdf_array", _user_pdf_array)):
+                if name not in own:
+                    setattr(cls, name, fn)
+        if "lnpdf" not in own:
+            if "_lnpdf" in own:
+                cls.lnpdf = _user_lnpdf_own
+            elif "_pdf" in own and not cls._ref_has_lnpdf:
+                cls.lnpdf = _user_lnpdf_from_pdf
 
     @property
     def bounds(self):
@@ -159,6 +229,7 @@ class Prior:
 class FlatPrior(Prior):
     kind = _cabi.PRIOR_FLAT
     bounded = 1
+    _ref_bounded = True
 
     def __init__(self, bounds):
         self._bounds = (float(bounds[0]), float(bounds[1]))
@@ -180,6 +251,7 @@ class FlatLogPrior(Prior):
     """pdf flat in 10**x (x is a log10 quantity)."""
     kind = _cabi.PRIOR_FLATLOG
     bounded = 1
+    _ref_bounded = True
 
     def __init__(self, bounds):
         self._bounds = (float(bounds[0]), float(bounds[1]))
@@ -199,6 +271,7 @@ class FlatLogPrior(Prior):
 class PowerLawPrior(Prior):
     kind = _cabi.PRIOR_POWERLAW
     bounded = 1
+    _ref_bounded = _ref_has_lnpdf = True
 
     def __init__(self, alpha, bounds):
         self.alpha = float(alpha)
@@ -234,6 +307,7 @@ class PowerLawPrior(Prior):
 
 class GaussianPrior(Prior):
     kind = _cabi.PRIOR_GAUSS
+    _ref_bounded = _ref_has_lnpdf = True
 
     def __init__(self, mean, sigma, bounds=None):
         self.mean, self.sigma = float(mean), float(sigma)
@@ -296,6 +370,7 @@ class GaussianPrior(Prior):
 
 class LogNormalPrior(Prior):
     kind = _cabi.PRIOR_LOGNORMAL
+    _ref_has_lnpdf = True
 
     def __init__(self, mu, sigma):
         self.mu, self.sigma = float(mu), float(sigma)
@@ -327,6 +402,7 @@ class ChabrierPrior(Prior):
     """Chabrier (2003) IMF: log-normal below the breakpoint, power law above, continuous at the
     breakpoint and normalised over ``bounds`` (reference: priors.py:143-232, 514-519)."""
     kind = _cabi.PRIOR_CHABRIER
+    _ref_has_lnpdf = True
 
     def __init__(self, bounds=(0.1, 100.0), mu=math.log(0.079), sigma=0.69 * math.log(10),
                  alpha=-2.35, breakpoint=1.0, powerlaw_bounds=(1.0, 100.0)):
@@ -553,10 +629,26 @@ DEVICE_PRIOR_TYPES = (FlatPrior, FlatLogPrior, PowerLawPrior, GaussianPrior, Log
                       ChabrierPrior, FehPrior)
 
 
+_DEVICE_ROUTE = {}       # class -> its instances take the device route (decided once per class)
+
+
+def _device_route(cls) -> bool:
+    if not issubclass(cls, DEVICE_PRIOR_TYPES):
+        return False
+    return not any(hook in k.__dict__ for k in _user_classes(cls) for hook in DENSITY_HOOKS)
+
+
 def is_host_prior(p) -> bool:
     """A prior object the device has no family for (a user's ``Prior`` subclass, a foreign object with ``lnpdf`` and
-    ``bounds``): evaluated on the host, parameter by parameter."""
-    return not isinstance(p, DEVICE_PRIOR_TYPES)
+    ``bounds``) - or one whose class derives from a device family and overrides one of :data:`DENSITY_HOOKS`, so that the
+    family's record no longer describes it: evaluated on the host, parameter by parameter.  This package's own classes,
+    and subclasses of them that only change ``__init__`` or ``sample``, are device priors."""
+    cls = type(p)
+    try:
+        return not _DEVICE_ROUTE[cls]
+    except KeyError:
+        route = _DEVICE_ROUTE[cls] = _device_route(cls)
+        return not route
 
 
 def check_host_prior(p, prop):

@@ -72,7 +72,7 @@ class EEPPrior:
 
     @orig_prior.setter
     def orig_prior(self, prior):
-        if not isinstance(prior, DEVICE_PRIOR_TYPES):
+        if is_host_prior(prior):
             raise NotImplementedError("prior %r is not evaluable on the device" % (prior,))
         self._orig_prior = prior
         _p.EPOCH[0] += 1
@@ -93,8 +93,10 @@ class _HostPriorMixin:
     starmodel.py:629-632; ``lnprior`` sums ``prior.lnpdf(value)`` over the parameters, :1616-1635).  The device evaluates a
     flat stand-in over such a prior's bounds (``priors.flat_stand_in``: the bounds test stays in the kernel); the model
     adds ``lnpdf(x) + log(width)`` of those parameters on the host to ``lnprior`` and ``lnpost`` - after the device's sum,
-    so the last bits differ from the reference's left-to-right sum (1e-15 relative; the parity tests' 1e-9 holds).  A
-    non-finite host term wins over whatever the device returned (the reference returns the prior when it is not finite).
+    so the last bits differ from the reference's left-to-right sum (1e-15 relative; the parity tests' 1e-9 holds).
+    ``lnprior`` is that sum whatever its terms are, as the reference's: NaN as soon as one term is NaN (an EEP term off the
+    grid, a NaN parameter), else -inf if one is; ``lnpost`` is -inf wherever a host term is not finite (the reference
+    returns -inf for every prior that is not finite, starmodel.py:538-542).
     Models with host priors are fitted by the framework-op sampler: the resident kernels cannot call back."""
 
     def _host_columns(self, name):          # parameter columns the prior of `name` applies to
@@ -125,17 +127,19 @@ class _HostPriorMixin:
         return hp
 
     @staticmethod
-    def _host_combine(out, hp):
-        """device lnprior / lnpost + host terms; a non-finite host term is the result."""
+    def _host_combine(out, hp, which):
+        """device lnpost (``which`` = 0) / lnprior (1) + host terms."""
         with np.errstate(invalid="ignore"):
-            return np.where(np.isfinite(hp), out + hp, hp)
+            return out + hp if which == 1 else np.where(np.isfinite(hp), out + hp, -np.inf)
 
     def _host_adjust_tensors(self, terms, pars, outs):
         """``outs``: (post, prior) CUDA tensors of the rows ``pars`` [n, n_params] (either may be None)."""
         import torch
         hp = torch.as_tensor(self._host_lnprior(terms, pars.detach().cpu().numpy()), device=pars.device)
-        fin = torch.isfinite(hp)
-        return tuple(None if o is None else torch.where(fin, o + hp, hp) for o in outs)
+        post, prior = outs
+        if post is not None:
+            post = torch.where(torch.isfinite(hp), post + hp, torch.full_like(hp, -math.inf))
+        return post, None if prior is None else prior + hp
 
 
 class _ScalarRow:
@@ -244,7 +248,8 @@ class _DeviceModelMixin(_HostPriorMixin):
             _cabi.check(rc)
         out = c.out
         if c.terms and which != 2:                       # priors evaluated on the host (_HostPriorMixin): add them
-            out = self._host_combine(out[:2], self._host_lnprior(c.terms, c.row[None, :]))
+            hp = self._host_lnprior(c.terms, c.row[None, :])[0]
+            out = (self._host_combine(out[0], hp, 0), self._host_combine(out[1], hp, 1))
         if which is None:
             return float(out[0]), float(out[1]), float(c.out[2])
         return float(out[which])
@@ -278,7 +283,7 @@ class _DeviceModelMixin(_HostPriorMixin):
             if which != 2:
                 terms = self._host_terms()
                 if terms:
-                    out = self._host_combine(out, self._host_lnprior(terms, a2))
+                    out = self._host_combine(out, self._host_lnprior(terms, a2), which)
             return float(out[0]) if single else out
         out = self._evaluate_device(dev.to_device_f64(a2, device), soa and not single, which != 0)
         out = (out if which == 0 else out[which]).cpu().numpy()

@@ -25,6 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from oracle import ref_harness as rh          # noqa: E402
+from oracle import user_priors                # noqa: E402
 from isochrones_amd import grids as G         # noqa: E402
 
 OUT = os.environ.get("ISO_GOLDEN_OUT") or os.path.join(ROOT, "tests", "golden")     # (override: tests/test_goldens_reproducible.py)
@@ -148,11 +149,38 @@ def _ref_prior(spec):
         return pr.FlatLogPrior(tuple(args))
     if fam == "PowerLaw":
         return pr.PowerLawPrior(args[0], tuple(args[1:3]))
+    if fam == "Chabrier":          # ("Chabrier", lo, hi): the reference's class takes nothing but bounds
+        return pr.ChabrierPrior(bounds=tuple(args[0:2]))
+    if fam == "Broken":            # ("Broken", mu, sigma, alpha, pl_lo, pl_hi, breakpoint, lo, hi)
+        return pr.BrokenPrior([pr.LogNormalPrior(args[0], args[1]), pr.PowerLawPrior(args[2], tuple(args[3:5]))],
+                              [args[5]], bounds=tuple(args[6:8]))
+    if fam == "Feh":               # ("Feh", halo_fraction, local, lo, hi)
+        p = pr.FehPrior(halo_fraction=args[0], local=bool(args[1]))
+        p.bounds = tuple(args[2:4])
+        return p
+    if fam == "User":              # ("User", class name, ...): oracle/user_priors.py on the reference's base classes
+        return user_priors.build(pr, spec)
     raise ValueError(fam)
 
 
+def edge_rows(centre, column, values):
+    """The centre row with one coordinate replaced, once per value."""
+    rows = np.repeat(np.asarray(centre, dtype=float)[None, :], len(values), axis=0)
+    rows[:, column] = values
+    return rows
+
+
+def _ulp_edges(prior, lo, hi, inner=()):
+    """(value, where, the reference must say) for a prior with bounds (lo, hi): on them, one ulp outside them, and
+    ``inner``, further (value, where, expectation) triples."""
+    return [(lo, "lo", "finite"), (hi, "hi", "finite"), (float(np.nextafter(lo, -np.inf)), "below lo", "-inf"),
+            (float(np.nextafter(hi, np.inf)), "above hi", "-inf")] + list(inner)
+
+
 def run_model_case(name, kind, n_stars, obs_key, model_table, bc_table, rng, n_wide, n_ball, extra_kw=None,
-                   priors=None, eep_orig_prior=None):
+                   priors=None, eep_orig_prior=None, edges=None, check=None):
+    """``edges`` (the prior-edge cases only): {parameter: [(value, where, expectation)]} - rows appended to the sampled
+    ones, the centre row with that one parameter replaced; ``check(arrays)``: further assertions of the generator."""
     sm = rh.ref("starmodel")
     limits = limits_of(kind, model_table[1])
     axes = model_table[1]
@@ -167,11 +195,20 @@ def run_model_case(name, kind, n_stars, obs_key, model_table, bc_table, rng, n_w
     if eep_orig_prior:             # the prior the EEP term transforms (priors.py:409-429) is an attribute
         mod._priors["eep"].orig_prior = _ref_prior(eep_orig_prior)
     pars = sample_pars(rng, kind, n_stars, axes, n_wide, n_ball)
+    edge_meta = []
+    if edges is not None:
+        centre = pars[2 * n_wide + n_ball]             # sample_pars' first hand-picked row
+        for par, triples in edges.items():
+            col = list(mod.param_names).index(par)
+            for v, where, expect in triples:
+                edge_meta.append(dict(row=int(pars.shape[0]), column=col, par=par, where=where, expect=expect))
+                pars = np.vstack([pars, edge_rows(centre, col, [v])])
     n = pars.shape[0]
     lnprior, lnlike, lnpost = np.empty(n), np.empty(n), np.empty(n)
     # math.log10(distance <= 0) raises under the pure-Python numba shim where compiled numba
     # follows libm (-inf / NaN); such direct lnlike calls are flagged and not compared.
     lnlike_undefined = np.zeros(n, dtype=bool)
+    lnpost_undefined = np.zeros(n, dtype=bool)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         with np.errstate(all="ignore"):
@@ -183,7 +220,14 @@ def run_model_case(name, kind, n_stars, obs_key, model_table, bc_table, rng, n_w
                 except ValueError:
                     lnlike[i] = np.nan
                     lnlike_undefined[i] = True
-                lnpost[i] = mod.lnpost(p)
+                if edges is None:
+                    lnpost[i] = mod.lnpost(p)
+                    continue
+                try:                                   # a prior that admits distance <= 0 lets lnpost reach that logarithm
+                    lnpost[i] = mod.lnpost(p)
+                except ValueError:
+                    lnpost[i] = np.nan
+                    lnpost_undefined[i] = True
     # the primary's interp_value / interp_mag at the same points
     prim = np.column_stack([pars[:, 0]] + [pars[:, n_stars + j] for j in range(4)])
     pcols = ["Teff", "logg", "feh", "Mbol"] + (["age", "dt_deep"] if kind == "track" else ["mass", "dm_deep"]) \
@@ -212,6 +256,31 @@ def run_model_case(name, kind, n_stars, obs_key, model_table, bc_table, rng, n_w
                interp_value=np.asarray(vals), Teff=Teff, logg=logg, feh=feh, mags=mags,
                cube_in=cube, cube_out=cube_out, lnlike_undefined=lnlike_undefined,
                mag_defined=good)
+    if edges is not None:
+        c = 2 * n_wide + n_ball
+        assert np.isfinite(lnpost[c]) and not lnpost_undefined[c], "%s: the centre row is not finite" % name
+        for e in edge_meta:
+            i = e["row"]
+            if e["expect"] == "finite":                # on or inside the prior's bounds: never flagged, never excluded
+                assert not (lnlike_undefined[i] or lnpost_undefined[i]), (name, e)
+                assert np.isfinite(lnprior[i]) and np.isfinite(lnpost[i]), (name, e, lnprior[i], lnpost[i])
+            elif e["expect"] == "-inf":
+                assert lnprior[i] == -np.inf and lnpost[i] == -np.inf, (name, e, lnprior[i], lnpost[i])
+        if check is not None:
+            check(dict(pars=pars, lnprior=lnprior, lnpost=lnpost, interp_value=np.asarray(vals), cols=pcols))
+        meta["edges"] = edge_meta
+        out["meta"] = json.dumps(meta)
+        out["lnpost_undefined"] = lnpost_undefined
+        # what the reference's base classes make of a user's prior, term by term: lnpdf(x), and prior(x) where it has one
+        for par, spec in (priors or {}).items():
+            if spec[0] != "User":
+                continue
+            pr, x = mod._priors[par], pars[:, list(mod.param_names).index(par)]
+            with warnings.catch_warnings(), np.errstate(all="ignore"):
+                warnings.simplefilter("ignore")
+                out["user_%s_lnpdf" % par] = np.array([pr.lnpdf(float(v)) for v in x], dtype=float)
+                if callable(pr):
+                    out["user_%s_call" % par] = np.array([pr(float(v)) for v in x], dtype=float)
     np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
     print("%-28s n=%d  finite lnpost=%d  -inf=%d  nan=%d" % (
         name, n, np.isfinite(lnpost).sum(), np.isneginf(lnpost).sum(), np.isnan(lnpost).sum()))
@@ -386,12 +455,12 @@ def run_tree_cases():
         _emit_tree_case(name, mod, kw, build is not None, rng, axes, limits, obs_mod)
 
 
-def _emit_tree_case(name, mod, kw, built, rng, axes, limits, obs_mod, extra_meta=None):
+def _emit_tree_case(name, mod, kw, built, rng, axes, limits, obs_mod, extra_meta=None, edges=None, n_rows=400):
     if True:
         names = list(mod.param_names)
         N = mod.obs.Nstars
         # parameter samples: per system descending eeps near the table's middle, some violations
-        n = 400
+        n = n_rows
         cols = []
         for s in mod.obs.systems:
             e = rng.uniform(axes[2][0] - 2, axes[2][-1] + 2, size=(n, N[s]))
@@ -403,6 +472,16 @@ def _emit_tree_case(name, mod, kw, built, rng, axes, limits, obs_mod, extra_meta
             cols.append(rng.uniform(-0.02, 1.02, (n, 1)))                                 # AV
         pars = np.hstack(cols)
         pars[0, 0] = np.nan
+        if edges is not None:                          # (centre row, {parameter: [(value, where, expectation)]})
+            centre, per_par = edges
+            edge_meta = []
+            pars = np.vstack([pars[:n_rows - 1], np.asarray(centre, dtype=float)[None, :]])
+            for par, triples in per_par.items():
+                col = names.index(par)
+                for v, where, expect in triples:
+                    edge_meta.append(dict(row=int(pars.shape[0]), column=col, par=par, where=where, expect=expect))
+                    pars = np.vstack([pars, edge_rows(centre, col, [v])])
+            n = pars.shape[0]
         lnprior, lnlike, lnpost = np.empty(n), np.empty(n), np.empty(n)
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
@@ -426,6 +505,16 @@ def _emit_tree_case(name, mod, kw, built, rng, axes, limits, obs_mod, extra_meta
                     bands=list(BANDS), built=built, systems=[int(s) for s in mod.obs.systems],
                     Nstars={str(k): int(v) for k, v in N.items()})
         meta.update(extra_meta or {})
+        if edges is not None:
+            c = n_rows - 1
+            assert np.isfinite(lnpost[c]), "%s: the centre row is not finite" % name
+            for e in edge_meta:
+                i = e["row"]
+                if e["expect"] == "finite":
+                    assert np.isfinite(lnprior[i]) and np.isfinite(lnpost[i]), (name, e, lnprior[i], lnpost[i])
+                else:
+                    assert lnprior[i] == -np.inf and lnpost[i] == -np.inf, (name, e, lnprior[i], lnpost[i])
+            meta["edges"] = edge_meta
         # StarModel.mnest_prior (starmodel.py:644-656) on non-degenerate cubes: unlike prior_transform it sorts every
         # system's EEPs in descending order.  Own generator, so the arrays above keep their values.
         import zlib
@@ -599,6 +688,79 @@ def run_prior_cases(rng=None):
                    eep_orig_prior=("LogNormal", float(np.log(0.9)), 0.5))
     run_model_case("iso_single_flatlog_age", "iso", 1, "spec_only", iso, bc, rng, 100, 100,
                    priors=dict(age=("FlatLog", 8.0, 10.0), distance=("PowerLaw", 2.0, 0.0, 500.0)))
+
+
+def _case_rng(name):
+    import zlib
+    return np.random.default_rng(zlib.crc32(name.encode()))      # per case: the older fixtures keep their draws
+
+
+def run_prior_edge_cases():
+    """Every route a prior takes, pinned on its branch points.  Device families with parameters the records must carry
+    (a broken prior = the device's Chabrier family with its own mu, sigma, alpha and breakpoint; FehPrior with a
+    halo fraction, disk and bounds of its own), the same families behind the EEP term (the ``prior(x)`` form), and priors
+    a user wrote (oracle/user_priors.py), which the reference itself normalises and evaluates here.  Besides a few hundred
+    sampled rows every case has the centre row with one parameter put ON each bound of its prior, one ulp outside it,
+    and for a broken prior on its breakpoint, one ulp below it and around the power law's own bounds.
+
+    One bound is open in the reference: ``BrokenPrior._lnpdf`` (priors.py:209-211) has no bounds test, so below its lower
+    bound ``lnpdf`` is the log-normal's value (the upper bound is closed by the power law's own test when both end there,
+    as here).  That row is recorded with the expectation "open" and compared like any other."""
+    trk, iso, bc = small_track(), small_iso(), small_bc()
+    inf = float("inf")
+    # --- device families ---
+    mu, sg, al, plo, phi, bp, lo, hi = float(np.log(0.3)), 0.5, -1.8, 0.6, 3.5, 0.9, 0.45, 3.5
+    up, dn = (lambda v: float(np.nextafter(v, np.inf))), (lambda v: float(np.nextafter(v, -np.inf)))
+    mass_edges = [(lo, "lo", "finite"), (hi, "hi", "finite"), (dn(lo), "below lo", "open"), (up(hi), "above hi", "-inf"),
+                  (bp, "breakpoint", "finite"), (float(np.nextafter(bp, 0)), "below breakpoint", "finite"),
+                  (plo, "power law lo", "finite"), (dn(plo), "below power law lo", "finite"),
+                  (up(plo), "above power law lo", "finite"), (dn(phi), "below power law hi", "finite")]
+    run_model_case("track_single_chabrier_feh", "track", 1, "phot_only", trk, bc, _case_rng("track_single_chabrier_feh"),
+                   100, 100,
+                   priors=dict(mass=("Broken", mu, sg, al, plo, phi, bp, lo, hi), feh=("Feh", 0.2, False, -0.8, 0.35),
+                               AV=("Gaussian", 0.3, 0.2, 0.05, 0.9)),
+                   # (the reference cannot CALL a Gaussian without bounds, priors.py:54-56 on bounds = None: infinite ones)
+                   eep_orig_prior=("Gaussian", 9.6, 0.3, -inf, inf),
+                   edges=dict(mass=mass_edges, feh=_ulp_edges("feh", -0.8, 0.35), AV=_ulp_edges("AV", 0.05, 0.9)))
+
+    obp = 0.215                    # (the synthetic isochrones put 0.17 - 0.35 solar masses at these EEPs)
+
+    def both_sides(a):
+        m = a["interp_value"][:, a["cols"].index("mass")]
+        fin = np.isfinite(a["lnprior"])
+        assert (fin & (m < obp)).sum() > 10 and (fin & (m >= obp)).sum() > 10, ((fin & (m < obp)).sum(), (fin & (m >= obp)).sum())
+        assert (np.isneginf(a["lnprior"]) & np.isfinite(m) & ((m < 0.18) | (m > 0.31))).sum() > 0    # outside its bounds
+
+    run_model_case("iso_binary_chabrier_orig", "iso", 2, "phot6_plx", iso, bc, _case_rng("iso_binary_chabrier_orig"), 100, 100,
+                   priors=dict(age=("Flat", 8.2, 9.7), feh=("Feh", 0.05, True, -0.7, 0.3)),
+                   eep_orig_prior=("Broken", float(np.log(0.2)), 0.3, -2.7, 0.19, 0.31, obp, 0.18, 0.31),
+                   edges=dict(age=_ulp_edges("age", 8.2, 9.7), feh=_ulp_edges("feh", -0.7, 0.3)), check=both_sides)
+    # --- a user's priors ---
+    tri_feh, far = ("User", "Triangle", -0.6, 0.4), ("User", "ForeignExp", 300.0, 5.0, 240.0)
+    run_model_case("track_single_user_priors", "track", 1, "spec_phot_plx", trk, bc, _case_rng("track_single_user_priors"),
+                   100, 100, priors=dict(feh=tri_feh, distance=far),
+                   edges=dict(feh=_ulp_edges("feh", -0.6, 0.4), distance=_ulp_edges("distance", 5.0, 240.0)))
+    run_model_case("iso_binary_user_priors", "iso", 2, "phot6_plx", iso, bc, _case_rng("iso_binary_user_priors"), 100, 100,
+                   priors=dict(AV=("User", "Triangle", 0.05, 0.8)), edges=dict(AV=_ulp_edges("AV", 0.05, 0.8)))
+    run_model_case("track_single_overriding_subclasses", "track", 1, "spec_phot_plx", trk, bc,
+                   _case_rng("track_single_overriding_subclasses"), 100, 100,
+                   priors=dict(feh=("User", "Skew", -0.1, 0.25, -0.7, 0.4), AV=("User", "Tilt", 0.02, 0.9),
+                               distance=("User", "Over", 2.0, 5.0, 240.0)),
+                   edges=dict(feh=_ulp_edges("feh", -0.7, 0.4), AV=_ulp_edges("AV", 0.02, 0.9),
+                              distance=_ulp_edges("distance", 5.0, 240.0)))
+    # --- the resolved binary of run_tree_cases with a user's AV prior (the generic model tests the bounds itself) ---
+    sm, obs_mod = rh.ref("starmodel"), rh.ref("observation")
+    axes = iso[1]
+    limits = limits_of("iso", axes)
+    name, build, kw = _tree_cases(obs_mod, None)[0]
+    assert name == "tree_resolved"
+    ic = rh.make_ref_ic("iso", iso, bc, limits, (axes[2][0], axes[2][-1]))
+    mod = sm.StarModel(ic, obs=build(name), **dict(kw))
+    spec = ("User", "Triangle", 0.05, 0.8)
+    mod.set_prior(AV=_ref_prior(spec))
+    _emit_tree_case("tree_resolved_user_av", mod, dict(kw), True, _case_rng("tree_resolved_user_av"), axes, limits, obs_mod,
+                    extra_meta=dict(priors=dict(AV=list(spec))), n_rows=200,
+                    edges=([185.0, 170.0, 9.4, -0.1, 500.0, 0.2], dict(AV_0=_ulp_edges("AV", 0.05, 0.8))))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -906,6 +1068,9 @@ def main():
     if "--only-priors" in sys.argv:
         run_prior_cases()
         return
+    if "--only-prior-edges" in sys.argv:
+        run_prior_edge_cases()
+        return
     if "--only-isotrack" in sys.argv:
         run_isotrack_case()
         return
@@ -952,6 +1117,7 @@ def main():
     run_prior_cases()
     run_ingest_cases()
     run_datadir_case()
+    run_prior_edge_cases()
 
 
 if __name__ == "__main__":

@@ -82,7 +82,9 @@ def _check_all_forms(mod, ref, x, host, tol=1e-12):
     for cols, user, _ in host.values():
         for c in cols:
             dead |= ~np.isfinite(_ln(user, x[:, c]))
-    want_prior = np.where(dead, -np.inf, want_prior)
+    # ... and lnprior is the reference's left-to-right sum there: NaN as soon as the EEP term is, whatever excludes the row
+    # (tests/test_gpu_user_priors.py holds that to the reference's own values)
+    want_prior = np.where(dead & ~np.isnan(ref.lnprior(x)), -np.inf, want_prior)
     ref_post = ref.lnpost(x)
     with np.errstate(invalid="ignore"):
         want_post = np.where(dead, -np.inf, np.where(np.isfinite(ref_post), want_prior + want_like, ref_post))
