@@ -53,6 +53,7 @@ extern "C" {
 #define ISO_MAX_STARS     3
 #define ISO_MAX_PARAMS    7   /* n_stars + 4 */
 #define ISO_MAX_COLS     64   /* columns selectable by one iso_interp call */
+#define ISO_MAX_GRID_BLOCKS 2048  /* the batch kernels' grid cap: workgroups of 256 lanes, the rest by striding */
 
 /* parametrisations (reference: isochrones/models.py:664-669, 691-696) */
 #define ISO_KIND_TRACK    0   /* (mass, eep, feh, distance, AV); grid axes (feh, mass, eep) */

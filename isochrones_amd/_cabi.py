@@ -12,6 +12,7 @@ ISO_MAX_BANDS = 32
 ISO_MAX_STARS = 3
 ISO_MAX_PARAMS = 7
 ISO_MAX_COLS = 64
+ISO_MAX_GRID_BLOCKS = 2048    # grid cap of the batch kernels (workgroups of 256 lanes); larger batches stride
 
 KIND_TRACK = 0
 KIND_ISO = 1

@@ -112,7 +112,7 @@ namespace {
 int grid_blocks(int64_t n)
 {
     int64_t b = (n + BLOCK - 1) / BLOCK;
-    const int64_t cap = 256 * 8;   // 256 CUs x 8 workgroups, grid-stride beyond that
+    const int64_t cap = ISO_MAX_GRID_BLOCKS;
     if (b > cap) b = cap;
     if (b < 1) b = 1;
     return (int)b;

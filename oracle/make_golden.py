@@ -346,6 +346,29 @@ def run_interp_kats(rng):
     print("interp_kats: 3d max|err vs func-free check skipped; %d + %d + %d points" % (len(pts), len(q), len(p4)))
 
 
+def run_interp_edges():
+    """The reference's DFInterpolator on the uniform-step tables of tests/_interp_twin.edge_tables() (U2, U3, U4: axes i*step
+    with a step that is no power of two, NaN nodes next to the probes where an O(1) index guess is off by one) at their node
+    and next-to-node probes.  Probes with a coordinate at the last node of an axis are left
+    out: the reference reads past the table there.  Only the probes and the answers are stored; the tables come from the
+    twin's fixed seeds."""
+    # the tables are made in one place, the test package's twin: this import needs the repository root on sys.path, which the
+    # head of this script puts there (also when tests/test_goldens_reproducible.py runs it in a subprocess)
+    from tests import _interp_twin as tw
+    out = {}
+    for name, t in tw.edge_tables(list(tw.UNIFORM)).items():
+        keep = np.ones(t.probes.shape[0], dtype=bool)
+        for d, a in enumerate(t.axes):
+            keep &= ~(t.probes[:, d] == a[-1])
+        pts = t.probes[keep]
+        dfi = rh.make_ref_dfinterp(t.grid, t.axes, t.columns)
+        with np.errstate(all="ignore"):
+            vals = dfi([pts[:, d] for d in range(t.nd)], t.columns)
+        out[name + "_pts"], out[name + "_vals"] = pts, np.asarray(vals, dtype=float)
+        print("interp_edges %s: %d points, %d finite values" % (name, pts.shape[0], np.isfinite(vals).sum()))
+    np.savez_compressed(os.path.join(OUT, "interp_edges.npz"), **out)
+
+
 def run_eep_case():
     """interp_eeps of the reference (isochrones/interp.py:488-558) on ragged age arrays built
     from a small synthetic track table whose EEP axis starts at 1 (the reference's assumption)."""
@@ -1080,6 +1103,9 @@ def main():
     if "--only-ini" in sys.argv:
         run_ini_cases()
         return
+    if "--only-interp-edges" in sys.argv:
+        run_interp_edges()
+        return
     if "--only-eep" in sys.argv:
         run_eep_case()
         return
@@ -1118,6 +1144,7 @@ def main():
     run_ingest_cases()
     run_datadir_case()
     run_prior_edge_cases()
+    run_interp_edges()
 
 
 if __name__ == "__main__":
