@@ -281,6 +281,8 @@ __global__ __launch_bounds__(BLOCK, 2) void k_chain_quantiles_select(const Quant
 //   refine   a target whose bin holds more (a chain with many repeats of one value, a narrow posterior): the bin's values
 //            are exactly those in [lo, hi] = their own min / max (the binning is monotone), so the same three steps run on
 //            that interval with the whole list area (2 048 values) as capacity - until it fits, or lo == hi (all equal).
+//            Every finite chain ends that way: where hi - lo or 4 096 / (hi - lo) is no finite double (ends near +-1.7e308,
+//            an interval narrower than 2^-1012), the round bins operands scaled by a power of two.
 // Every pass streams the pair's values from memory (the W values of a step are contiguous in the parameter-major chain);
 // a 30 000-value pair is 240 KB - L2 / Infinity Cache hits after the first pass.  Bit for bit numpy.percentile.
 // (Round 6, measured and not kept: ONE pass that also keeps the values of sampled WINDOWS around each level in LDS and ranks
@@ -294,6 +296,7 @@ constexpr int QBIG_POOL = QSEL_RANKS * QBIG_CAP;           // = the single list 
 constexpr size_t QBIG_LDS = (size_t)QBIG_POOL * 8 + QBIG_BINS * 4 + QBIG_BINS + 6 * QSEL_RANKS * 4 + 16 * 8 + 8 * 4 + QSEL_RANKS * 8;
 constexpr int QBIG_UN = 4;                                 // loads in flight per lane and round (2 and 8: the same time)
 constexpr int QBIG_NS = 16;                                // sampled values per thread (up to 4 096 per pair)
+constexpr int QBIG_ROUNDS = 256;                           // bound of the refinement loop (more than any float64 chain needs)
 struct QbigValues { double v[QBIG_UN]; };
 
 __global__ __launch_bounds__(BLOCK, 4) void k_chain_quantiles_big(const QuantArgs A)
@@ -460,7 +463,12 @@ __global__ __launch_bounds__(BLOCK, 4) void k_chain_quantiles_big(const QuantArg
     }
     __syncthreads();
     const bool binned = mx > mn;                             // (exact range: false = every finite value equal, or none)
-    const double inv = binned ? (double)QBIG_BINS / (mx - mn) : 0.0;
+    // (a range beyond the largest double: its reciprocal from the halved ends, so that the values still spread over the bins -
+    // v - mn may then be inf, which the clamp below sends to the last bin; a range whose reciprocal overflows: the largest
+    // double, never inf, so that (v - mn) * inv is no NaN at v = mn.  Both are monotone, which is all a binning has to be.)
+    double inv = binned ? (double)QBIG_BINS / (mx - mn) : 0.0;
+    if (binned && !isfinite(mx - mn)) inv = (double)QBIG_BINS / (mx * 0.5 - mn * 0.5) * 0.5;
+    inv = fmin(inv, 0x1.fffffffffffffp1023);
     // (clamped: values outside a sampled range belong to the end bins; the comparison form also keeps the conversion in range)
     auto bin_of = [&](double v) { return (int)fmin(fmax((v - mn) * inv, 0.0), (double)(QBIG_BINS - 1)); };
     if (binned) {
@@ -551,15 +559,11 @@ __global__ __launch_bounds__(BLOCK, 4) void k_chain_quantiles_big(const QuantArg
                 }
             }
             block_minmax(lo, hi);
-            for (int round = 0; round < 64; ++round) {       // (each round splits the interval 4 096 ways: a few at most)
-                if (!(hi > lo)) {
-                    if (tid == 0) result[k] = lo;
-                    break;
-                }
+            // one round on [lo, hi] with the monotone binning bin2 (lo -> bin 0, hi -> the last bin): true = the target's sub-bin
+            // fitted the pool and result[k] is written; false = [lo, hi] and want now describe that sub-bin
+            auto refine_round = [&](auto bin2) {
                 for (int i = tid; i < QBIG_BINS; i += BLOCK) hist[i] = 0;
                 __syncthreads();
-                const double inv2 = (double)QBIG_BINS / (hi - lo);
-                auto bin2 = [&](double v) { return min(QBIG_BINS - 1, (int)((v - lo) * inv2)); };
                 QBIG_FOR_VALUES(v) {
                     if (v >= lo && v <= hi) atomicAdd(&hist[bin2(v)], 1);
                 }
@@ -579,7 +583,7 @@ __global__ __launch_bounds__(BLOCK, 4) void k_chain_quantiles_big(const QuantArg
                     }
                     __syncthreads();
                     select_in_list(lists, list_count[0], want2, k, tid, BLOCK);
-                    break;
+                    return true;
                 }
                 double lo2 = d_inf(), hi2 = -d_inf();
                 QBIG_FOR_VALUES(v) {
@@ -592,6 +596,34 @@ __global__ __launch_bounds__(BLOCK, 4) void k_chain_quantiles_big(const QuantArg
                 lo = lo2;
                 hi = hi2;
                 want = want2;
+                return false;
+            };
+            // Each round splits the interval 4 096 ways and keeps one part (lo and hi lie in different parts, so the interval
+            // shrinks every time): a few rounds for any chain a sampler writes, at most 175 for the 2 098 binades between the
+            // smallest and the largest double - QBIG_ROUNDS is never reached, and no target leaves the loop unresolved.
+            for (int round = 0; round < QBIG_ROUNDS; ++round) {
+                if (!(hi > lo)) {
+                    if (tid == 0) result[k] = lo;
+                    break;
+                }
+                const double width = hi - lo;                // workgroup-uniform, as everything up to the choice of the form
+                const double inv2 = (double)QBIG_BINS / width;
+                bool done;
+                if (isfinite(width) && isfinite(inv2)) {
+                    done = refine_round([&](double v) { return min(QBIG_BINS - 1, (int)((v - lo) * inv2)); });
+                } else {
+                    // hi - lo is beyond the largest double, or so small that its reciprocal is: the same binning on operands
+                    // scaled by a power of two (exact; 2^-2 brings any range into the doubles, 2^600 lifts an interval
+                    // narrower than 2^-1012 - whose ends are then below 2^-959 - to where its reciprocal is finite).  Clamped by
+                    // comparison: no conversion sees a value out of range.
+                    const double sc = isfinite(width) ? 0x1p600 : 0.25;
+                    const double los = lo * sc, invs = (double)QBIG_BINS / (hi * sc - los);
+                    done = refine_round([&](double v) {
+#pragma clang fp contract(off)   // (v * sc is exact unless it underflows; rounded on its own either way)
+                        return (int)fmin(fmax((v * sc - los) * invs, 0.0), (double)(QBIG_BINS - 1));
+                    });
+                }
+                if (done) break;
             }
             __syncthreads();
         }
