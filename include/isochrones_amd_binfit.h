@@ -12,7 +12,14 @@
  * Definition.  Per row h: hmx = max_b lnh[h][b] and u_b = exp(lnh[h][b] - hmx), 0 for a cell of height 0 (that header's u,
  * word for word).  Per (row, star), over ascending b from 0.0 with a separate multiply and add,
  *     s1[h][s] = sum_b u_b * A[b][s].
- * Star s is live for row h if it is unmasked and s1 > 0.  For a live star
+ * Rescue (isochrones_amd_binned.h gives the reason and the argument for the threshold): an unmasked star whose s1 is below
+ * ISO_BINNED_RESCUE_BELOW = 2^-400, 0 included, is taken again relative to its own largest height.  A row's height is also
+ * kept as u_b = m_b * 2^k_b with k_b = rint((lnh_b - hmx) / ln 2), at least -2^30, and m_b = u_b / 2^k_b (exact) where u_b is
+ * a normal number, exp((lnh_b - hmx) - k_b ln 2) with ln 2 in two parts where it is not; m_b is in [0.70, 1.42], 0 for a
+ * cell of height 0.  With kmax the largest k_b over the cells with A[b][s] > 0 and m_b > 0, the star's products become
+ *     u_b * A[b][s] := (m_b * 2^(k_b - kmax)) * A[b][s]   over those cells, 0.0 in the others,
+ * and s1 their sum over ascending b from 0.0 (0 if there is no such cell).  The common factor 2^kmax cancels in p.
+ * Star s is live for row h if it is unmasked and s1 > 0: exactly where ell of iso_binned_lnlike is finite.  For a live star
  *     p[s][b] = (u_b * A[b][s]) / s1,
  * the posterior probability that the star lies in cell b; a star that is not live has p = 0 in every cell.  Over the live
  * stars, in ascending s, each sum from 0.0:
@@ -27,7 +34,9 @@
  * Summation order of the device kernels.  k_binfit_partial gives a workgroup of 256 lanes one (chunk of ISO_BINFIT_CHUNK
  * consecutive stars, row).  It takes the chunk's stars in ascending order a tile of ISO_BINFIT_TILE at a time: the tile's
  * u_b * A[b][s] is staged in LDS, one lane per star adds its s1 over ascending b, and every entry is divided by its
- * star's s1 (0 where the star is not live).  Every output has one owner lane: lane 64 + b owns N_b, and the B (B + 1) / 2
+ * star's s1 (0 where the star is not live); the lane that added a star's s1 writes a rescued star's products over the staged
+ * ones before the division (the m_b of the row wait in the tile's pad column, written once per workgroup), by the function the host
+ * entry calls.  Every output has one owner lane: lane 64 + b owns N_b, and the B (B + 1) / 2
  * pairs b <= b' are dealt out in blocks of 3 x 3 cells, block (I, J), I <= J, numbered row by row, to lane number of the
  * block (at most 253 blocks of at most 9 pairs a lane; a lane reads six values a star for its nine products).  An owner
  * walks the tile's stars in ascending order and adds p[s][b], or p[s][b] * p[s][b'] with a separate multiply and add, to

@@ -43,7 +43,26 @@
  * for a cell of height 0: the exps are taken once per row, not per star.  Per (row, star), over ascending b, each from 0.0:
  *     s1 = sum_b u_b * A[b][s],   s2 = sum_b (u_b * u_b) * A2[b][s],
  *     ell[h][s] = (mx[s] + hmx) + ln s1 - ln M,   ess[h][s] = s1 * s1 / s2.
- * If s1 is not > 0: ell = -inf, ess = 0.  A masked star has ell = ess = NaN.  ell and ess are [H][n_ens].  L[h] and
+ * If s1 is not > 0: ell = -inf, ess = 0.  A masked star has ell = ess = NaN.
+ *
+ * Rescue.  hmx belongs to the row, so a star whose table lies only in cells far below the row's top has products
+ * u_b * A[b][s] that leave float64's range while its answer is well inside it: from 372 nats below the top u_b * u_b is 0
+ * (ess = 0 / 0), from 708 u_b is subnormal, from 745 it is 0 (ell = -inf).  So a (row, star) whose s1 above is below
+ * ISO_BINNED_RESCUE_BELOW = 2^-400 (0 included) is taken again with the star's own reference height,
+ *     ref = max{lnh_b : A[b][s] > 0 and lnh_b > -inf},   u'_b = exp(lnh_b - ref) over those cells,
+ *     s1 = sum_b u'_b * A[b][s],   s2 = sum_b (u'_b * u'_b) * A2[b][s]   (ascending b, each from 0.0),
+ *     ell[h][s] = (mx[s] + ref) + ln s1 - ln M,   ess[h][s] = s1 * s1 / s2;
+ * without such a cell ell = -inf and ess = 0 as before.  The largest term of the new s1 is A of the reference cell itself,
+ * so ell and ess are those of exact arithmetic wherever the star has weight under the row.  The threshold: at s1 >= 2^-400
+ * every term the ordinary sums lose is harmless.  A term of s1 with a subnormal u_b is off by at most 2^-1074 * A[b][s] <=
+ * 2^-1043 (A <= M < 2^31), 2^-643 of s1.  A term of s2 whose u_b * u_b is subnormal or 0 is off by at most 2^-1022 *
+ * A2[b][s] <= 2^-991, while s2 >= s1 * s1 / M >= 2^-831 (Cauchy-Schwarz over the star's at most M samples): 2^-154 of s2
+ * for all 64 cells together.  And s1 * s1 >= 2^-800 is a normal number.  The threshold is far above the point where any of
+ * this matters and far below any s1 an ordinary row produces, so a pair that does not take the rescue keeps the bits of the
+ * formula above.  What remains deliberate is the compression's single mx per star: a table entry that underflowed there is
+ * 0 here too, and an A2 entry that is 0 under a positive A gives the ess it gave before.
+ *
+ * ell and ess are [H][n_ens].  L[h] and
  * min_ess[h] are isochrones_amd_hier.h's, over the unmasked stars of ell and ess as they stand after the call (0 and +inf
  * when there is none; both or neither).  M is an argument (int64), so that a call on the table of an injection set passes
  * the number of injections.
@@ -56,7 +75,8 @@
  * layout, the batch and the range of stars; no floating-point atomics, no per-lane histograms.  k_binned_rows gives a
  * workgroup a tile of ISO_BINNED_ROW_TILE consecutive rows and a block of 256 stars, a lane one star: it adds over
  * ascending b with a separate multiply and add; a row's arithmetic does not depend on its place in the tile, nor a star's
- * on its block.  k_binned_total is k_hier_total: lane i adds the unmasked stars s = i, i + 256, ... in ascending order,
+ * on its block.  The lane that owns a star takes a rescued pair again after the tile's ordinary results, from the tables and
+ * the row in global memory, by the function the host entry calls: the same ascending order, and the same identities.  k_binned_total is k_hier_total: lane i adds the unmasked stars s = i, i + 256, ... in ascending order,
  * then the xor butterfly inside each wavefront (distances 32, 16, ..., 1), then ((v0 + v1) + v2) + v3.  The source writes
  * no fused multiply-add and is compiled with -ffp-contract=off.  So a star's A, A2 and mx are the same bits alone, in any
  * batch, in any sub-range of stars, from either layout, from a column and from a copy of it in another storage with a
@@ -87,6 +107,8 @@ extern "C" {
 #define ISO_BINNED_MAX_AXES 2
 /* hyper rows a workgroup of k_binned_rows takes; no part of the summation order */
 #define ISO_BINNED_ROW_TILE 8
+/* a (row, star) whose s1 is below this, 0 included, is taken again with the star's own reference height (Contraction) */
+#define ISO_BINNED_RESCUE_BELOW 0x1p-400
 
 const char* iso_binned_version(void);
 const char* iso_binned_last_error(void);

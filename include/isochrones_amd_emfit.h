@@ -13,6 +13,16 @@
  * Definition.  Per replicate r, with g = its row of g0 and t = 0, 1, ...:
  *   1. v_b = g_b * scale_b.
  *   2. Per star, over ascending b from 0.0 with a separate multiply and add: s1 = sum_b v_b * A[b][s].
+ *      Rescue: v is not normalised, and a fit drives the mass of an unsupported cell geometrically to 0, so a star whose
+ *      table lies only in such cells has an s1 that is tiny, subnormal or 0 while w / s1 is beyond float64.  A star that is
+ *      unmasked with w > 0 and whose s1 is below ISO_BINNED_RESCUE_BELOW = 2^-400 (0 included; isochrones_amd_binned.h has
+ *      the argument for the threshold) takes its products again as mantissas and powers of two: with frexp's g_b = mg 2^eg,
+ *      scale_b = ms 2^es and A[b][s] = ma 2^ea, the product is ((mg * ms) * ma) * 2^(eg + es + ea); emax is the largest of
+ *      these exponents over the cells where both mg * ms and A[b][s] are above 0, and
+ *          v_b * A[b][s] := ldexp((mg * ms) * ma, eg + es + ea - emax),   s1 their sum over ascending b from 0.0,
+ *          log(s1) := log(s1) + emax * ln 2   (ln 2 its nearest float64),
+ *      so that w / s1 and every product of step 4 are those of the star scaled by 2^-emax, which cancels.  No factor is
+ *      rounded before it is scaled: a subnormal g_b enters with all its bits.  Without such a cell s1 = 0.
  *   3. Star s is live if it is unmasked, w[r][s] > 0 and s1 > 0.  Anything else, a NaN included, adds nothing.
  *   4. Over the live stars, each sum from 0.0:
  *        Q_t    = sum_s w * log(s1)
@@ -32,7 +42,8 @@
  * the kernel.  Lane l owns the stars s = l (mod 256) and takes them in ascending order into sums of its own that start at
  * 0.0 with every t: Q, W, the live count and one sum per cell.  A live star's s1 is taken in a first pass over ascending
  * b; a second pass over ascending b reads the star's column again and adds (v_b * A[b][s]) * (w / s1) to the cell's sum,
- * w / s1 rounded once.  The 256 lane sums of each output are combined within each wavefront of 64 lanes by xor butterflies
+ * w / s1 rounded once; a rescued star goes through the same two passes with its scaled products (a cell's mg * ms and
+ * eg + es are kept in LDS next to v, taken once per step).  The 256 lane sums of each output are combined within each wavefront of 64 lanes by xor butterflies
  * of distances 32 .. 1 (wave_sum of common/wave_reduce.h), and the four wavefront totals are added in ascending wavefront
  * order from the first.  T and g_b = N_b / T are the definition's.  No floating-point atomics; the source writes no fused
  * multiply-add and is compiled with -ffp-contract=off.  So a replicate's outputs are the same bits alone, in any batch,

@@ -12,13 +12,15 @@
 //                     nine products a star; one pair a read pair would be eighteen).  A tile row
 //                     is LDP = 65 doubles: at the same star the 64 cells fall into the 64 banks two by two, which is what a
 //                     64-bit read allows, and at the same cell (the staging writes) consecutive stars are 130 words apart,
-//                     again two a bank; with a row of 64 doubles every star of a cell would share one bank.
+//                     again two a bank; with a row of 64 doubles every star of a cell would share one bank.  The pad, column
+//                     64 of row b, keeps cell b's height as a mantissa for the rescue of the header (split_m below).
 //   k_binfit_total    one workgroup per row: every output's owner adds the chunks in ascending order, a pair's sum goes to
 //                     both halves of C, and the chunks' live counts are added.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "isochrones_amd_binfit.h"
@@ -53,6 +55,46 @@ __host__ __device__ inline void pair_of(int k, int B, int& b, int& b2) {
 // the number of the pair (b, b2), b <= b2
 __host__ __device__ inline int pair_number(int b, int b2, int B) { return b * B - b * (b - 1) / 2 + (b2 - b); }
 
+constexpr int NO_TERM = INT32_MIN;              // the largest power of two of a star without weight under the row
+constexpr double LN2_HI = 0x1.62e42feep-1;      // ln 2 in two parts: k * LN2_HI is exact for |k| < 2^21
+constexpr double LN2_LO = 0x1.a39ef35793c76p-33;
+
+// u = exp(l - hmx) as m * 2^k for the header's rescue: k = rint((l - hmx) / ln 2), at least -2^30; m = u / 2^k (exact) where
+// u is a normal number, the exp of the rest where it is not; m is in [0.70, 1.42], or 0.0 for a cell of height 0 (and for one
+// more than 2^30 powers of two below the row's top)
+__host__ __device__ inline int split_k(double l, double hmx, double& kd) {
+    kd = fmax(rint((l - hmx) * 1.4426950408889634), -1073741824.0);
+    return (int)kd;
+}
+
+__host__ __device__ inline double split_m(double l, double hmx, double u) {
+    if (!(l > neg_inf())) return 0.0;
+    double kd;
+    const int k = split_k(l, hmx, kd);
+    return (u >= 0x1p-1022) ? ldexp(u, -k) : exp(((l - hmx) - kd * LN2_HI) - kd * LN2_LO);
+}
+
+// the header's rescue of one star under one row: p_b = m_b * 2^(k_b - kmax) * A[b][s] with 2^kmax the largest power of two
+// over the cells the star has weight in, written to p[0 .. B); returns their sum over ascending b from 0.0 (0.0: no such
+// cell).  m[b * stride]: the row's split_m.  Host and device run this one function
+__host__ __device__ inline double rescue_star(const double* A, size_t ld, size_t s, const double* row, double hmx,
+                                              const double* m, int stride, int B, double* p) {
+    double kd;
+    int kmax = NO_TERM;
+#pragma unroll 1
+    for (int b = 0; b < B; ++b)
+        if (A[(size_t)b * ld + s] > 0.0 && m[b * stride] > 0.0) kmax = max(kmax, split_k(row[b], hmx, kd));
+    double s1 = 0.0;
+#pragma unroll 1
+    for (int b = 0; b < B; ++b) {
+        const double a = A[(size_t)b * ld + s], mb = m[b * stride];
+        const double v = (a > 0.0 && mb > 0.0) ? ldexp(mb, split_k(row[b], hmx, kd) - kmax) * a : 0.0;
+        p[b] = v;
+        s1 += v;
+    }
+    return s1;
+}
+
 // the workspace: [H][nc][B + NP] doubles (NP = 0 without pairs), then [H][nc] int32 live counts
 struct Args {
     const double* A;
@@ -82,6 +124,7 @@ __global__ void __launch_bounds__(BLOCK) k_binfit_partial(const Args P) {
     if (tid < B) {
         const double l = row[tid];
         s_u[tid] = (l > neg_inf()) ? exp(l - hmx) : 0.0;
+        s_p[tid * LDP + MAXB] = split_m(l, hmx, s_u[tid]);           // for the rescue, in the tile's pad column
     }
     // the lane's block of pairs: the cells [SIDE * I, SIDE * I + SIDE) x [SIDE * J, SIDE * J + SIDE), I <= J, the blocks
     // numbered row by row.  A cell past B is read as cell B - 1 (computed, never written)
@@ -128,7 +171,15 @@ __global__ void __launch_bounds__(BLOCK) k_binfit_partial(const Args P) {
             double s1 = 0.0;
 #pragma unroll 8
             for (int b = 0; b < B; ++b) s1 += s_p[lane * LDP + b];
-            const bool live = in && (!P.mask || P.mask[s] != 0) && s1 > 0.0;
+            const bool on = in && (!P.mask || P.mask[s] != 0);
+            bool live = on && s1 > 0.0;
+            // rare: a star whose s1 is below the threshold (0 included) is taken again relative to its own largest height
+            if (__ballot(on && s1 < ISO_BINNED_RESCUE_BELOW) != 0ull) {             // the same branch for the wavefront
+                if (on && s1 < ISO_BINNED_RESCUE_BELOW) {                           // not a NaN
+                    s1 = rescue_star(P.A, ld, (size_t)s, row, hmx, s_p + MAXB, LDP, B, s_p + lane * LDP);
+                    live = s1 > 0.0;
+                }
+            }
             s_s1[lane] = live ? s1 : 0.0;
             nlive += __popcll(__ballot(live));
         }
@@ -270,7 +321,7 @@ int iso_binfit_moments_host(const double* A, int32_t B, int32_t n_ens, const dou
     for (size_t i = 0; i < (size_t)H * B; ++i)
         if (lnh[i] == HUGE_VAL) return fail(ISO_BINFIT_ERR_INVALID, who, "a log cell density is +inf");
     const size_t ld = (size_t)n_ens;
-    std::vector<double> u(B), p(B);
+    std::vector<double> u(B), p(B), um(B);
     for (int h = 0; h < H; ++h) {
         double hmx = neg_inf();
         for (int b = 0; b < B; ++b) {
@@ -280,6 +331,7 @@ int iso_binfit_moments_host(const double* A, int32_t B, int32_t n_ens, const dou
         for (int b = 0; b < B; ++b) {
             const double l = lnh[(size_t)h * B + b];
             u[b] = (l > neg_inf()) ? exp(l - hmx) : 0.0;
+            um[b] = split_m(l, hmx, u[b]);
         }
         double* Nh = N + (size_t)h * B;
         double* Ch = C ? C + (size_t)h * B * B : nullptr;
@@ -294,6 +346,7 @@ int iso_binfit_moments_host(const double* A, int32_t B, int32_t n_ens, const dou
                 p[b] = u[b] * A[(size_t)b * ld + s];
                 s1 += p[b];
             }
+            if (s1 < ISO_BINNED_RESCUE_BELOW) s1 = rescue_star(A, ld, (size_t)s, lnh + (size_t)h * B, hmx, um.data(), 1, B, p.data());
             if (!(s1 > 0.0)) continue;
             ++live;
             for (int b = 0; b < B; ++b) {

@@ -13,6 +13,8 @@
 //                      every lane: broadcasts.
 //   k_binned_rows      one workgroup per (tile of ROW_TILE rows, block of 256 stars), lane = star: the tile's
 //                      u = exp(lnh - hmx) and u * u in LDS, then per cell one load of A and A2 and eight multiplies and adds.
+//                      A (row, star) whose s1 is below ISO_BINNED_RESCUE_BELOW is taken again by its lane after the tile's
+//                      stores, with the star's own reference height (the header's rescue): rare, and no part of the loop.
 //   k_binned_total     one workgroup per row: L and min_ess over the unmasked stars in a fixed order (common/hier_block.h, as
 //                      k_hier_total).
 #include <hip/hip_runtime.h>
@@ -222,6 +224,31 @@ __global__ void __launch_bounds__(BLOCK) k_binned_compress(const CArgs A) {
     }
 }
 
+// the contraction of one (row, star) taken again with the star's own reference height (the header's rescue): ref is the
+// largest lnh_b over the cells the star has weight in.  Host and device run this one function
+__host__ __device__ inline void rescue_pair(const double* A, const double* A2, size_t ld, int s, const double* row, int B,
+                                            double mx, double lnM, double& ell, double& ess) {
+    double ref = neg_inf();
+    for (int b = 0; b < B; ++b) {
+        const double l = row[b];
+        if (A[(size_t)b * ld + s] > 0.0 && l > neg_inf()) ref = fmax(ref, l);       // a NaN is a cell of height 0
+    }
+    ell = neg_inf();
+    ess = 0.0;
+    if (!(ref > neg_inf())) return;
+    double s1 = 0.0, s2 = 0.0;
+    for (int b = 0; b < B; ++b) {
+        const double a = A[(size_t)b * ld + s], l = row[b];
+        if (a > 0.0 && l > neg_inf()) {
+            const double u = exp(l - ref);
+            s1 += u * a;
+            s2 += (u * u) * A2[(size_t)b * ld + s];
+        }
+    }
+    ell = ((mx + ref) + log(s1)) - lnM;
+    ess = (s1 * s1) / s2;
+}
+
 struct RArgs {
     const double* A;
     const double* A2;
@@ -234,7 +261,7 @@ struct RArgs {
     int32_t B, H, n_ens, ens_begin, n_ens_out, nsb;
 };
 
-__global__ void __launch_bounds__(BLOCK) k_binned_rows(const RArgs R) {
+__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) k_binned_rows(const RArgs R) {
     __shared__ double s_u[RT * MAXB];           // [j][b]: exp(lnh - hmx) of row j of the tile
     __shared__ double s_uu[RT * MAXB];
     __shared__ double s_hmx[RT];
@@ -291,13 +318,24 @@ __global__ void __launch_bounds__(BLOCK) k_binned_rows(const RArgs R) {
         }
     }
     const double mx = R.mx[s], lnM = log((double)R.M);
+    unsigned again = 0u;                        // the rows of the tile whose s1 is below the rescue's threshold (0 included)
 #pragma unroll
     for (int j = 0; j < RT; ++j)
         if (h0 + j < H) {
             const bool none = !(s1[j] > 0.0);
             R.ell[(size_t)(h0 + j) * ld + s] = none ? neg_inf() : ((mx + s_hmx[j]) + log(s1[j])) - lnM;
             R.ess[(size_t)(h0 + j) * ld + s] = none ? 0.0 : (s1[j] * s1[j]) / s2[j];
+            again |= (s1[j] < ISO_BINNED_RESCUE_BELOW) ? (1u << j) : 0u;      // not a NaN
         }
+    // rare: the pair is taken again from the tables, by the lane that owns it, in the same ascending order
+    while (again) {
+        const int j = __ffs(again) - 1;
+        again &= again - 1u;
+        double ell, ess;
+        rescue_pair(R.A, R.A2, ld, s, R.lnh + (size_t)(h0 + j) * B, B, mx, lnM, ell, ess);
+        R.ell[(size_t)(h0 + j) * ld + s] = ell;
+        R.ess[(size_t)(h0 + j) * ld + s] = ess;
+    }
 }
 
 __global__ void __launch_bounds__(BLOCK) k_binned_total(const double* __restrict__ ell, const double* __restrict__ ess,
@@ -552,6 +590,9 @@ int iso_binned_lnlike_host(const double* A, const double* A2, const double* mx, 
             const bool none = !(s1 > 0.0);
             ell[(size_t)h * ld + s] = none ? neg_inf() : ((mx[s] + hmx) + log(s1)) - lnM;
             ess[(size_t)h * ld + s] = none ? 0.0 : (s1 * s1) / s2;
+            if (s1 < ISO_BINNED_RESCUE_BELOW)
+                rescue_pair(A, A2, ld, s, lnh + (size_t)h * B, B, mx[s], lnM, ell[(size_t)h * ld + s],
+                            ess[(size_t)h * ld + s]);
         }
     }
     if (L) row_totals_host(ell, ess, mask, n_ens, H, L, min_ess);

@@ -11,13 +11,17 @@
 //                     lane keeps one sum per cell in registers, BP of them (the grid padded to 8, 16, 32 or 64 cells, so
 //                     that every index is a constant); a star's s1 is taken in a first pass over the cells and its terms
 //                     in a second pass that reads the star's column again from the cache, eight cells' loads at a
-//                     time, so no table value is held from pass to pass.  Every lane takes the stop / step decision from the same LDS words, so the
-//                     whole workgroup leaves the loop in the same iteration and every barrier is met by all of it.
+//                     time, so no table value is held from pass to pass.  A star whose s1 is below
+//                     ISO_BINNED_RESCUE_BELOW goes through the same two passes with its products scaled by a power of two
+//                     (the header's rescue; a cell's mantissa and exponent wait in LDS next to v).  Every lane takes the
+//                     stop / step decision from the same LDS words, so the whole workgroup leaves the loop in the same
+//                     iteration and every barrier is met by all of it.
 //   k_emfit_weights   one lane per (replicate, star): one Philox call, a count or a logarithm, one store.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "isochrones_amd_emfit.h"
@@ -57,10 +61,37 @@ __host__ __device__ inline int decide(int live, int t, double Q, double Qprev, d
     return ISO_EMFIT_RUNNING;
 }
 
+// the header's rescue works on g_b * scale_b * A[b][s] as a mantissa and a power of two, so that no factor and no product
+// leaves float64's range: the cell's part, taken once per step (m in [0.25, 1), or 0 for a cell without height)
+__host__ __device__ inline void split_height(double g, double scale, double& m, int& e) {
+    int eg, es;
+    const double mg = frexp(g, &eg), ms = frexp(scale, &es);
+    m = mg * ms;
+    e = eg + es;
+}
+
+// m * 2^e * a as a power of two: its exponent, for a product that is not 0
+__host__ __device__ inline int term_exponent(int e, double a) {
+    int ea;
+    (void)frexp(a, &ea);
+    return e + ea;
+}
+
+// m * 2^e * a / 2^emax; 0.0 if either factor is 0.0, or if the product lies more than 1074 powers of two below 2^emax
+__host__ __device__ inline double scaled_term(double m, int e, double a, int emax) {
+    int ea;
+    const double ma = frexp(a, &ea);
+    return ldexp(m * ma, e + ea - emax);
+}
+
+constexpr int NO_TERM = INT32_MIN;              // the largest exponent of a star without a product above 0
+constexpr double LN2 = 0.6931471805599453;      // float64's nearest to ln 2
+
 template <int BP>
 __global__ void __launch_bounds__(BLOCK, 2) k_emfit_run(const Args P) {
     __shared__ double s_v[MAXB];                // g_b * scale_b of the current step
-    __shared__ double s_g[MAXB];
+    __shared__ double s_vm[MAXB];               // the same heights as a mantissa and a power of two, for the rescue
+    __shared__ int s_ve[MAXB];
     __shared__ double s_N[MAXB];
     __shared__ double s_part[WAVES][MAXB + 2];  // the wavefronts' totals: the cells, then Q and W
     __shared__ double s_Q, s_W, s_prev;
@@ -80,13 +111,17 @@ __global__ void __launch_bounds__(BLOCK, 2) k_emfit_run(const Args P) {
             s_prev = *(const volatile double*)(P.objective + r);
         }
     }
+    double g_mine = 0.0;                        // g of cell tid
     if (tid < B) {
         const double* from = P.first ? P.g0 + r * (size_t)P.g0_stride : P.g + r * (size_t)B;
         const double gb = *(const volatile double*)(from + tid);
-        s_g[tid] = gb;
+        g_mine = gb;
         s_v[tid] = gb * P.scale[tid];
+        split_height(gb, P.scale[tid], s_vm[tid], s_ve[tid]);
     } else if (tid < MAXB) {
         s_v[tid] = 0.0;                         // the cells past the grid that a group of the second pass reads
+        s_vm[tid] = 0.0;
+        s_ve[tid] = 0;
     }
     __syncthreads();
     if (s_status != ISO_EMFIT_RUNNING) return;  // the same word for every lane
@@ -110,7 +145,8 @@ __global__ void __launch_bounds__(BLOCK, 2) k_emfit_run(const Args P) {
                 s1 += p;
             }
             const double wt = wr ? wr[s] : 1.0;
-            if ((!P.mask || P.mask[s] != 0) && wt > 0.0 && s1 > 0.0) {
+            const bool counts = (!P.mask || P.mask[s] != 0) && wt > 0.0;
+            if (counts && s1 >= ISO_BINNED_RESCUE_BELOW) {
                 const double term = wt * log(s1);
                 q += term;
                 ws += wt;
@@ -140,6 +176,49 @@ __global__ void __launch_bounds__(BLOCK, 2) k_emfit_run(const Args P) {
                             const double p = s_v[at + b0 + j] * a[j];
                             const double add = p * ratio;
                             acc[b0 + j] += add;
+                        }
+                    }
+                }
+            } else if (counts && s1 < ISO_BINNED_RESCUE_BELOW) {
+                // rare: s1 is below the threshold (0 included; a NaN is not, and adds nothing).  The star's products are taken again relative to its
+                // largest one, 2^emax, in the same order and into the same sums
+                int emax = NO_TERM;
+                pc = col;
+#pragma unroll 1
+                for (int b = 0; b < B; ++b, pc += ld) {
+                    const double a = *pc;
+                    if (a > 0.0 && s_vm[b] > 0.0) emax = max(emax, term_exponent(s_ve[b], a));
+                }
+                if (emax != NO_TERM) {
+                    double r1 = 0.0;
+                    pc = col;
+#pragma unroll 1
+                    for (int b = 0; b < B; ++b, pc += ld) {
+                        const double p = scaled_term(s_vm[b], s_ve[b], *pc, emax);
+                        r1 += p;
+                    }
+                    const double term = wt * (log(r1) + (double)emax * LN2);
+                    q += term;
+                    ws += wt;
+                    ++nl;
+                    const double ratio = wt / r1;
+                    int at = 0;
+                    asm volatile("" : "+v"(at));
+                    int nb = B;
+                    asm volatile("" : "+s"(nb));
+                    const int last = nb - 1;
+#pragma unroll
+                    for (int b0 = 0; b0 < BP; b0 += GROUP) {
+                        if (b0 < nb) {
+                            double a[GROUP];
+#pragma unroll
+                            for (int j = 0; j < GROUP; ++j) a[j] = col[(size_t)min(b0 + j, last) * ld];
+#pragma unroll
+                            for (int j = 0; j < GROUP; ++j) {
+                                const double p = scaled_term(s_vm[at + b0 + j], s_ve[at + b0 + j], a[j], emax);
+                                const double add = p * ratio;
+                                acc[b0 + j] += add;
+                            }
                         }
                     }
                 }
@@ -176,8 +255,9 @@ __global__ void __launch_bounds__(BLOCK, 2) k_emfit_run(const Args P) {
             double T = 0.0;
             for (int b = 0; b < B; ++b) T += s_N[b];
             const double gb = s_N[tid] / T;
-            s_g[tid] = gb;
+            g_mine = gb;
             s_v[tid] = gb * P.scale[tid];
+            split_height(gb, P.scale[tid], s_vm[tid], s_ve[tid]);
         }
         Qprev = Q;
         ++t;
@@ -186,7 +266,7 @@ __global__ void __launch_bounds__(BLOCK, 2) k_emfit_run(const Args P) {
         if (done == P.steps && t < P.max_iter) break;   // the next launch goes on from the outputs
     }
 
-    if (tid < B) P.g[r * (size_t)B + tid] = s_g[tid];
+    if (tid < B) P.g[r * (size_t)B + tid] = g_mine;
     if (tid == 0) {
         P.objective[r] = Q;
         P.n_iter[r] = t;
@@ -330,7 +410,8 @@ int iso_emfit_run_host(const double* A, int32_t B, int32_t n_ens, const double* 
         }
         if (!(sum > 0.0)) return fail(ISO_EMFIT_ERR_INVALID, who, "a row of g0 must sum to something above 0");
     }
-    std::vector<double> gr(B), v(B), N(B);
+    std::vector<double> gr(B), v(B), N(B), vm(B);
+    std::vector<int> ve(B);
     for (int r = 0; r < R; ++r) {
         for (int b = 0; b < B; ++b) gr[b] = g0[(size_t)r * g0_stride + b];
         const double* wr = w ? w + (size_t)r * ld : nullptr;
@@ -339,6 +420,7 @@ int iso_emfit_run_host(const double* A, int32_t B, int32_t n_ens, const double* 
         for (;;) {
             for (int b = 0; b < B; ++b) {
                 v[b] = gr[b] * scale[b];
+                split_height(gr[b], scale[b], vm[b], ve[b]);
                 N[b] = 0.0;
             }
             Q = 0.0;
@@ -351,7 +433,32 @@ int iso_emfit_run_host(const double* A, int32_t B, int32_t n_ens, const double* 
                     s1 += p;
                 }
                 const double wt = wr ? wr[s] : 1.0;
-                if (!((!mask || mask[s] != 0) && wt > 0.0 && s1 > 0.0)) continue;
+                if (!((!mask || mask[s] != 0) && wt > 0.0)) continue;
+                if (s1 != s1) continue;
+                if (s1 < ISO_BINNED_RESCUE_BELOW) {
+                    int emax = NO_TERM;
+                    for (int b = 0; b < B; ++b) {
+                        const double a = A[(size_t)b * ld + s];
+                        if (a > 0.0 && vm[b] > 0.0) emax = std::max(emax, term_exponent(ve[b], a));
+                    }
+                    if (emax == NO_TERM) continue;
+                    double r1 = 0.0;
+                    for (int b = 0; b < B; ++b) {
+                        const double p = scaled_term(vm[b], ve[b], A[(size_t)b * ld + s], emax);
+                        r1 += p;
+                    }
+                    const double term = wt * (log(r1) + (double)emax * LN2);
+                    Q += term;
+                    W += wt;
+                    ++live;
+                    const double ratio = wt / r1;
+                    for (int b = 0; b < B; ++b) {
+                        const double p = scaled_term(vm[b], ve[b], A[(size_t)b * ld + s], emax);
+                        const double add = p * ratio;
+                        N[b] += add;
+                    }
+                    continue;
+                }
                 const double term = wt * log(s1);
                 Q += term;
                 W += wt;

@@ -207,7 +207,9 @@ BINNED = KernelLibrary(
     #: are two registers, since a lane owns one cell.  The column index is a run-time loop, as in k_reweight_weights.  Its 24
     #: spilled SGPRs (the argument block) go to VGPR lanes, not to scratch.  The kernel runs once per (catalog, edges), so the
     #: budget is what it compiles to, the 5-waves-per-SIMD one: 96 VGPRs, and no scratch at all.  k_binned_rows (the sums of
-    #: eight rows, 32 registers, and one cell's two loads) is 55 VGPRs at 8 waves with 8.1 KB of LDS (the tile's u and u * u);
+    #: eight rows, 32 registers, and one cell's two loads) is 55 VGPRs at 8 waves with 8.1 KB of LDS (the tile's u and u * u),
+    #: and 64 with the header's rescue behind it (a rare per-lane tail with an exp and a log), held at 8 waves by
+    #: amdgpu_waves_per_eu(8, 8) without scratch;
     #: k_binned_total is k_hier_total: 17 VGPRs at 8 waves
     max_vgpr=96, min_waves=5, extra_headers=_RECORD_HEADERS + _COLUMN_HEADERS + ("common/hier_block.h",))
 
@@ -263,7 +265,7 @@ BINFIT = KernelLibrary(
     name="binfit", flags=_NO_CONTRACT,
     #: every kernel the library compiles (tests/test_binfit_library.py pins this set)
     kernels=("k_binfit_partial", "k_binfit_total"),
-    #: k_binfit_partial compiles to 120 VGPRs, no scratch, 33.5 KB of LDS and 4 waves per SIMD.  A lane holds the sums of its
+    #: k_binfit_partial compiles to 124 VGPRs (120 before the header's rescue), no scratch, 33.5 KB of LDS and 4 waves per SIMD.  A lane holds the sums of its
     #: block of 3 x 3 pairs and of its cell (20 registers), the six places of the block's cells in a tile row, the sixteen
     #: loads of its star's cells that a tile issues together (32, with their addresses) and, in the walk unrolled over two
     #: stars, their twelve 64-bit LDS reads in flight (24).  The waves are set by the LDS, not by the registers: a tile of
@@ -286,8 +288,8 @@ EMFIT = KernelLibrary(
     name="emfit", flags=_NO_CONTRACT,
     #: every kernel the library compiles (tests/test_emfit_library.py pins this set)
     kernels=("k_emfit_run<8>", "k_emfit_run<16>", "k_emfit_run<32>", "k_emfit_run<64>", "k_emfit_weights"),
-    #: k_emfit_run<64> compiles to 208 VGPRs, no scratch, no spill, 3.7 KB of LDS and 2 waves per SIMD; <32> to 144 (3 waves),
-    #: <16> to 110 and <8> to 100 (4).  A lane holds one sum per cell of the padded grid (2 BP registers: 128 at 64 cells), the
+    #: k_emfit_run<64> compiles to 220 VGPRs, no scratch, no spill, 3.9 KB of LDS and 2 waves per SIMD; <32> to 157 (3 waves),
+    #: <16> to 122 and <8> to 106 (4); before the header's rescue 208, 144, 110 and 100 with 3.7 KB.  A lane holds one sum per cell of the padded grid (2 BP registers: 128 at 64 cells), the
     #: star's Q, W and live sums, the eight loads a pass has in flight with their addresses, and an inlined log and division.
     #: Left alone the compiler lifts the BP heights of the second pass and the BP comparisons with B out of the star loop
     #: (254 VGPRs, 260 B of scratch and 107 spilled SGPRs at 64 cells): above 16 cells the heights are read from LDS per

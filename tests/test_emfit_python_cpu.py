@@ -141,6 +141,26 @@ def test_the_slices_of_a_small_budget_give_the_same_replicates():
         assert getattr(sliced, k).tobytes() == getattr(whole, k).tobytes(), k
 
 
+def test_a_bootstrap_from_a_start_with_a_subnormal_cell_has_finite_masses():
+    """Point-like chains with one star alone in the first bin, and replicates that share one start row whose first cell has
+    the subnormal mass 1e-310 (what an earlier fit leaves of a cell it has emptied): w / s1 of that star is beyond float64,
+    and its products are taken again relative to their largest (include/isochrones_amd_emfit.h).  Every replicate has
+    finite masses, counts that star where its weight is above 0, and ends at the weighted counts over the weights' sum."""
+    counts = np.array([1, 20, 15, 14])
+    S, R = int(counts.sum()), 12
+    pp = _point_like(counts)
+    w = emfit.star_weights("poisson", 5, 1, R, S)
+    w[0] = 1.0
+    assert (w[:, 0] > 0).any() and (w[:, 0] == 0).any()
+    g, objective, n_iter, status, n_live = pp.em_masses(weights=w, g0=np.array([1e-310, 0.4, 0.3, 0.3]))
+    assert np.isfinite(g).all() and np.isfinite(objective).all() and (status == ec.CONVERGED).all()
+    assert np.array_equal(n_live, (w > 0).sum(axis=1))
+    cells = np.repeat(np.arange(4), counts)
+    for r in range(R):
+        wc = np.bincount(cells, weights=w[r], minlength=4)
+        assert np.all(np.abs(g[r] - wc / wc.sum()) <= 1e-12), r
+
+
 # -- the noisy catalog of section 24 at a seed whose maximum is on the boundary ---------------------------------------
 LO, HI, SIGMA = 0.0, 6.0, 1.0
 EDGES = np.array([0.0, 0.8, 1.7, 3.0, 3.6, 4.9, 6.0])
