@@ -16,7 +16,7 @@ from .catalog import (StarCatalog, CatalogPosterior, fit_catalog, synthetic_cata
                       select_multiplicity)
 from . import priors, grids, ingest, mist, nested, ini, persist, utils
 from .starfit import starfit, batch_starfit
-from .cluster import StarClusterModel, simulate_cluster
+from .cluster import StarClusterModel, combine_star_moments, simulate_cluster
 from .diagnostics import chain_diagnostics, ChainDiagnostics
 from .derived import chain_derived
 from .predictive import chain_predictive

@@ -4,7 +4,9 @@ table of member stars (reference: isochrones/cluster.py:182-477, cluster_utils.p
 The per-EEP columns of every parameter row come from the device interpolators (``interp_device`` / ``interp_mag_device``
 over ``[rows x EEPs]`` points); the half-filled (primary EEP, secondary EEP) grid of every member star, its two trapezoid
 integrals and the sum over stars run in libiso_cluster.so (include/isochrones_amd_cluster.h).  Priors are seven scalars
-per row and are evaluated on the host.  Deviations from the reference ("Star clusters"): the property term
+per row and are evaluated on the host.  What a fit says about each member star - moments of the same grid's integrand -
+comes from libiso_members.so (include/isochrones_amd_members.h): ``star_moments``, ``star_posteriors``,
+:func:`combine_star_moments`; the reference has no counterpart.  Deviations from the reference ("Star clusters"): the property term
 is read in its documented ``[star, eep]`` layout, ``bounds()`` falls back to finite boxes for gamma and feh, ``set_prior``
 works."""
 from __future__ import annotations
@@ -48,6 +50,40 @@ def _lnpdf_vec(pr, x):
                 out = np.where((x < pr.bounds[0]) | (x > pr.bounds[1]), -np.inf, out)
             return out
     return P.lnpdf_array(pr, x)
+
+
+#: the columns of :meth:`StarClusterModel.star_posteriors` and the keys of :func:`combine_star_moments`
+STAR_POSTERIOR_COLUMNS = ("eep_A", "eep_A_sd", "mass_A", "mass_A_sd", "q", "q_sd", "mass_B", "mass_B_sd", "p_pair", "p_single",
+                          "q_pair", "n_rows", "n_dead")
+
+
+def combine_star_moments(ln_like, moments):
+    """Per-star summaries from :meth:`StarClusterModel.star_moments` of ``P`` parameter rows (numpy only): ``ln_like [P,
+    N_s]``, ``moments [P, N_s, 11]`` -> dict of ``[N_s]`` arrays keyed by :data:`STAR_POSTERIOR_COLUMNS`.
+
+    The rows are equally weighted posterior draws, so a star's raw moments average linearly over them; a row whose
+    ``ln_like`` for the star is not finite (its likelihood is 0 there, or NaN) is skipped for that star.  ``n_rows`` is the
+    number of rows averaged and ``n_dead`` the number skipped (``n_rows + n_dead == P``); a star without a live row has NaN
+    everywhere else.  Means are the averaged first moments, standard deviations ``sqrt(max(E[x^2] - E[x]^2, 0))`` (0, not NaN,
+    when the variance rounds below 0), ``p_pair`` / ``p_single`` the averaged state weights and ``q_pair = E[q pair] / p_pair``
+    the mass ratio given a pair (NaN where ``p_pair`` is 0)."""
+    ln_like = np.asarray(ln_like, dtype=float)
+    moments = np.asarray(moments, dtype=float)
+    if ln_like.ndim != 2 or moments.shape != ln_like.shape + (11,):
+        raise ValueError("need ln_like [P, N_s] and moments [P, N_s, 11] (got %s and %s)" % (ln_like.shape, moments.shape))
+    live = np.isfinite(ln_like)
+    n_rows = live.sum(axis=0)
+    with np.errstate(all="ignore"):
+        mean = np.where(live[:, :, None], moments, 0.0).sum(axis=0) / n_rows[:, None]       # 0 / 0 = NaN without a live row
+        out = {}
+        for name, i in (("eep_A", 0), ("mass_A", 2), ("q", 4), ("mass_B", 6)):
+            out[name] = mean[:, i]
+            out[name + "_sd"] = np.sqrt(np.maximum(mean[:, i + 1] - mean[:, i] * mean[:, i], 0.0))
+        out["p_pair"], out["p_single"] = mean[:, 8], mean[:, 9]
+        out["q_pair"] = np.where(mean[:, 8] == 0, np.nan, mean[:, 10] / np.where(mean[:, 8] == 0, 1.0, mean[:, 8]))
+    out["n_rows"] = n_rows.astype(np.int64)
+    out["n_dead"] = (ln_like.shape[0] - n_rows).astype(np.int64)
+    return {k: out[k] for k in STAR_POSTERIOR_COLUMNS}
 
 
 class StarClusterModel(_NestedFitMixin):
@@ -183,12 +219,68 @@ class StarClusterModel(_NestedFitMixin):
             self._dev[device] = st
         return st
 
-    def _rows_per_chunk(self, n_eep):
+    def _rows_per_chunk(self, n_eep, work_fold=1):
+        """Rows per call; ``work_fold``: inner integrals per (row, star, EEP) of the call's scratch buffer."""
         if self.chunk_rows:
             return max(1, int(self.chunk_rows))
         nb, npr, ns = len(self.bands), len(self.props), len(self.stars)
-        per_row = 8 * n_eep * (ns + 2 * (3 + 2 * nb + npr) + 2 * nb + 16)
+        per_row = 8 * n_eep * (work_fold * ns + 2 * (3 + 2 * nb + npr) + 2 * nb + 16)
         return max(1, DEFAULT_CHUNK_BYTES // per_row)
+
+    def _chunk_columns(self, x, st, device):
+        """The C ABI's ``(cols [p, ncol, ne], n_valid [p], rowpar [p, 4])`` of the rows ``x`` (CUDA float64 ``[p, 7]``): what
+        ``iso_cluster_lnlike`` and ``iso_members_moments`` both read."""
+        import torch
+        E = st["eeps"]
+        ne = E.numel()
+        nb, npr = len(self.bands), len(self.props)
+        ncol = 3 + 2 * nb + npr
+        mass_lo, mass_hi = (float(v) for v in self.bounds("mass"))
+        interp = self.ic.model_grid.interp
+        p = x.shape[0]
+        age = x[:, 0:1].expand(p, ne).reshape(-1).contiguous()
+        feh = x[:, 1:2].expand(p, ne).reshape(-1).contiguous()
+        eep = E.repeat(p).contiguous()
+        # the interpolation library switches to packed-table kernels (other rounding) for calls of 1 024 points or
+        # more; slices below that keep every point on the same kernel, so a row's columns - and its lnlike - are
+        # bit-identical however the rows are batched
+        pts = p * ne
+        sl = [(a, min(a + INTERP_SLICE, pts)) for a in range(0, pts, INTERP_SLICE)]
+        vals = torch.cat([interp.interp_device([age[a:b], feh[a:b], eep[a:b]], st["icols"], device)
+                          for a, b in sl])                                          # [p*ne, 2 + props]
+        dist = x[:, 2:3].expand(p, ne).reshape(-1)
+        AV = x[:, 3:4].expand(p, ne).reshape(-1)
+        five = torch.stack([eep, age, feh, dist, AV])
+        mags = torch.cat([self.ic.interp_mag_device(five[:, a:b].contiguous(), list(self.bands), device)[3]
+                          for a, b in sl])                                          # [p*ne, nb]
+        mass = vals[:, 0].view(p, ne)
+        valid = torch.isfinite(mass)
+        order = torch.sort((~valid).to(torch.int8), dim=1, stable=True).indices     # kept EEPs first, in order
+        n_valid = valid.sum(dim=1).to(torch.int32).contiguous()
+        take = lambda t: torch.gather(t, 1, order)                                   # noqa: E731
+        alpha, gamma, fB = x[:, 4:5], x[:, 5:6], x[:, 6:7]
+        a1 = alpha + 1.0
+        m_c = take(mass)
+        mass_term = ((torch.log(a1 / (mass_hi ** a1 - mass_lo ** a1)) + alpha * torch.log(m_c))
+                     + torch.log(torch.abs(take(vals[:, 1].view(p, ne)))))
+        mag_c = torch.gather(mags.view(p, ne, nb), 1, order[:, :, None].expand(p, ne, nb)).transpose(1, 2)
+        cols = torch.empty((p, ncol, ne), dtype=torch.float64, device=x.device)
+        cols[:, 0] = E[order]
+        cols[:, 1] = m_c
+        cols[:, 2] = mass_term
+        cols[:, 3:3 + nb] = torch.pow(10.0, -0.4 * mag_c)
+        cols[:, 3 + nb:3 + 2 * nb] = mag_c
+        k = 2
+        for j, q in enumerate(self.props):
+            if q == "parallax":
+                cols[:, 3 + 2 * nb + j] = (1000.0 / x[:, 2:3]).expand(p, ne)
+            else:
+                cols[:, 3 + 2 * nb + j] = take(vals[:, k].view(p, ne))
+                k += 1
+        g1 = gamma + 1.0
+        rowpar = torch.cat([torch.log(fB), torch.log(1.0 - fB), gamma,
+                            torch.log(g1 / (1.0 - self.minq ** g1))], dim=1).contiguous()
+        return cols, n_valid, rowpar
 
     def lnlike_device(self, pars, star_terms=False):
         """lnlike of the rows of a CUDA float64 tensor ``[P, 7]`` -> CUDA tensor ``[P]`` (and ``ln like_s`` ``[P, N_s]``
@@ -198,62 +290,17 @@ class StarClusterModel(_NestedFitMixin):
         device = pars.device.index
         pars = pars.to(torch.float64).contiguous()
         st = self._device_state(device)
-        E = st["eeps"]
-        ne = E.numel()
+        ne = st["eeps"].numel()
         ns, nb, npr = len(self.stars), len(self.bands), len(self.props)
-        ncol = 3 + 2 * nb + npr
-        mass_lo, mass_hi = (float(v) for v in self.bounds("mass"))
         n = pars.shape[0]
         out = torch.empty(n, dtype=torch.float64, device=pars.device)
         per_star = torch.empty((n, ns), dtype=torch.float64, device=pars.device) if star_terms else None
-        interp = self.ic.model_grid.interp
         lib = CC.lib()
         chunk = self._rows_per_chunk(ne)
         for c0 in range(0, n, chunk):
             x = pars[c0:c0 + chunk]
             p = x.shape[0]
-            age = x[:, 0:1].expand(p, ne).reshape(-1).contiguous()
-            feh = x[:, 1:2].expand(p, ne).reshape(-1).contiguous()
-            eep = E.repeat(p).contiguous()
-            # the interpolation library switches to packed-table kernels (other rounding) for calls of 1 024 points or
-            # more; slices below that keep every point on the same kernel, so a row's columns - and its lnlike - are
-            # bit-identical however the rows are batched
-            pts = p * ne
-            sl = [(a, min(a + INTERP_SLICE, pts)) for a in range(0, pts, INTERP_SLICE)]
-            vals = torch.cat([interp.interp_device([age[a:b], feh[a:b], eep[a:b]], st["icols"], device)
-                              for a, b in sl])                                          # [p*ne, 2 + props]
-            dist = x[:, 2:3].expand(p, ne).reshape(-1)
-            AV = x[:, 3:4].expand(p, ne).reshape(-1)
-            five = torch.stack([eep, age, feh, dist, AV])
-            mags = torch.cat([self.ic.interp_mag_device(five[:, a:b].contiguous(), list(self.bands), device)[3]
-                              for a, b in sl])                                          # [p*ne, nb]
-            mass = vals[:, 0].view(p, ne)
-            valid = torch.isfinite(mass)
-            order = torch.sort((~valid).to(torch.int8), dim=1, stable=True).indices     # kept EEPs first, in order
-            n_valid = valid.sum(dim=1).to(torch.int32).contiguous()
-            take = lambda t: torch.gather(t, 1, order)                                   # noqa: E731
-            alpha, gamma, fB = x[:, 4:5], x[:, 5:6], x[:, 6:7]
-            a1 = alpha + 1.0
-            m_c = take(mass)
-            mass_term = ((torch.log(a1 / (mass_hi ** a1 - mass_lo ** a1)) + alpha * torch.log(m_c))
-                         + torch.log(torch.abs(take(vals[:, 1].view(p, ne)))))
-            mag_c = torch.gather(mags.view(p, ne, nb), 1, order[:, :, None].expand(p, ne, nb)).transpose(1, 2)
-            cols = torch.empty((p, ncol, ne), dtype=torch.float64, device=pars.device)
-            cols[:, 0] = E[order]
-            cols[:, 1] = m_c
-            cols[:, 2] = mass_term
-            cols[:, 3:3 + nb] = torch.pow(10.0, -0.4 * mag_c)
-            cols[:, 3 + nb:3 + 2 * nb] = mag_c
-            k = 2
-            for j, q in enumerate(self.props):
-                if q == "parallax":
-                    cols[:, 3 + 2 * nb + j] = (1000.0 / x[:, 2:3]).expand(p, ne)
-                else:
-                    cols[:, 3 + 2 * nb + j] = take(vals[:, k].view(p, ne))
-                    k += 1
-            g1 = gamma + 1.0
-            rowpar = torch.cat([torch.log(fB), torch.log(1.0 - fB), gamma,
-                                torch.log(g1 / (1.0 - self.minq ** g1))], dim=1).contiguous()
+            cols, n_valid, rowpar = self._chunk_columns(x, st, device)
             work = torch.empty(p * ns * ne, dtype=torch.float64, device=pars.device)
             o = out[c0:c0 + p]
             ps = per_star[c0:c0 + p] if star_terms else None
@@ -267,6 +314,75 @@ class StarClusterModel(_NestedFitMixin):
                 ev[1].record()
                 self._kernel_events.append(ev)
         return (out, per_star) if star_terms else out
+
+    def star_moments_device(self, pars):
+        """``(ln like_s [P, N_s], moments [P, N_s, 11])`` of the rows of a CUDA float64 tensor ``[P, 7]``, as CUDA tensors
+        (see :meth:`star_moments`)."""
+        import torch
+        from . import _members_cabi as MC
+        device = pars.device.index
+        pars = pars.to(torch.float64).contiguous()
+        st = self._device_state(device)
+        ne = st["eeps"].numel()
+        ns, nb, npr = len(self.stars), len(self.bands), len(self.props)
+        n = pars.shape[0]
+        ln_like = torch.empty((n, ns), dtype=torch.float64, device=pars.device)
+        moments = torch.empty((n, ns, MC.NMOM), dtype=torch.float64, device=pars.device)
+        lib = MC.lib()
+        chunk = self._rows_per_chunk(ne, work_fold=MC.NINNER)
+        for c0 in range(0, n, chunk):
+            x = pars[c0:c0 + chunk]
+            p = x.shape[0]
+            cols, n_valid, rowpar = self._chunk_columns(x, st, device)
+            work = torch.empty(p * ns * MC.NINNER * ne, dtype=torch.float64, device=pars.device)
+            MC.check(lib.iso_members_moments(dev.ptr(cols), ne, p, dev.ptr(n_valid), dev.ptr(rowpar), dev.ptr(st["val"]),
+                                             dev.ptr(st["w"]), ns, nb, npr, self.minq, dev.ptr(work),
+                                             dev.ptr(ln_like[c0:c0 + p]), dev.ptr(moments[c0:c0 + p]),
+                                             dev.stream_ptr(device)))
+        return ln_like, moments
+
+    def star_moments(self, p):
+        """What the rows ``p`` (``[P, 7]`` or a 7-vector) say about each member star: ``(ln_like [P, N_s], moments [P, N_s,
+        11])``, CUDA tensors for a CUDA ``p`` and numpy otherwise.  ``ln_like`` is :meth:`lnlike_stars`'s per-star term bit
+        for bit; the moments are expectations under the normalised integrand of star s's likelihood over its (primary EEP,
+        secondary EEP) grid (include/isochrones_amd_members.h), in the order of ``_members_cabi.MOMENTS``: the primary's EEP
+        and its square, the primary's mass and its square, the mass ratio q and its square, the secondary's mass and its
+        square, ``p_pair``, ``p_single`` and E[q pair].  A star whose likelihood is 0 has ``-inf`` and eleven NaNs.
+
+        The model mixes pair and single *per band*: ``p_pair`` is the weight of the state in which every band's light is
+        the pair's, ``p_single`` that in which every band's is the primary's alone.  With one band they sum to 1; with more
+        the rest is the weight of the mixed states.  That is a property of the model, not of this code.  q and the
+        secondary's mass are integrated over the whole grid whatever the state, so they carry information only where
+        ``p_pair`` is high; the mass ratio given a pair is moment 10 over moment 8.  Rows are evaluated in chunks sized by a
+        budget that counts the six-fold inner-integral buffer (or ``chunk_rows``)."""
+        import torch
+        if dev.is_tensor(p) and p.is_cuda:
+            return self.star_moments_device(p.to(torch.float64).reshape(-1, self.n_params))
+        x = np.ascontiguousarray(np.asarray(p, dtype=float).reshape(-1, self.n_params))
+        x_t = torch.as_tensor(x, dtype=torch.float64, device=torch.device("cuda", dev.current_device()))
+        ln_like, moments = self.star_moments_device(x_t)
+        return ln_like.cpu().numpy(), moments.cpu().numpy()
+
+    def star_posteriors(self, p=None, max_rows=256):
+        """Per-star summaries of a fit: a DataFrame indexed like ``stars`` with the columns :data:`STAR_POSTERIOR_COLUMNS`
+        (:func:`combine_star_moments` of :meth:`star_moments`).  ``p`` defaults to the fit's ``samples``, thinned to at most
+        ``max_rows`` evenly spaced rows; with no ``p`` and no fit it raises ``ValueError``."""
+        import pandas as pd
+        if p is None:
+            try:
+                frame = self.samples
+            except AttributeError:
+                raise ValueError("star_posteriors needs parameter rows p or a fit (fit_mcmc, fit_multinest)") from None
+            x = np.asarray(frame[list(self.param_names)], dtype=float)
+            if x.shape[0] > max_rows:
+                x = x[np.linspace(0, x.shape[0] - 1, int(max_rows)).round().astype(int)]
+            p = x
+        ln_like, moments = self.star_moments(p)
+        if dev.is_tensor(ln_like):
+            ln_like, moments = ln_like.cpu().numpy(), moments.cpu().numpy()
+        out = combine_star_moments(ln_like, moments)
+        index = getattr(getattr(self.stars, "df", None), "index", None)
+        return pd.DataFrame({k: out[k] for k in STAR_POSTERIOR_COLUMNS}, index=index)
 
     def _evaluate(self, p, which, star_terms=False):
         import torch

@@ -303,6 +303,25 @@ EMFIT = KernelLibrary(
     extra_headers=("../../include/isochrones_amd_binned.h", "../../include/isochrones_amd_hier.h", "common/last_error.h",
                    "common/philox.h", "common/wave_reduce.h"))
 
+# per-star moments of the star-cluster likelihood's integrand (csrc/members/): what a cluster fit says about each member
+# star.  k_cluster_pairs's plan with six running trapezoids a lane instead of one, and an outer pass that turns them into
+# ln like_s and eleven moments.  It shares no source with CLUSTER (whose header list and kernel set are pinned): the cell
+# arithmetic is restated, and ln_like being the same bits as CLUSTER's lnlike_star is what its GPU test holds the two to
+# -ffp-contract=off: every product and sum is rounded as written (no fused multiply-adds), which that bit identity and
+# the header's summation order rest on (a (row, star) result is bit-identical alone, in any batch and on every call)
+MEMBERS = KernelLibrary(
+    name="members", flags=_NO_CONTRACT,
+    #: every kernel the library compiles (tests/test_members_library.py pins this set)
+    kernels=("k_members_finish", "k_members_pairs"),
+    #: k_members_pairs compiles to 120 VGPRs, no scratch, (4 N_b + 3) x 64 doubles + 64 ints of dynamic LDS (7.9 KB at 3
+    #: bands, 67.3 KB at 32) and 4 waves per SIMD: k_cluster_pairs's 78 and on top five more running trapezoids with their
+    #: previous products (20 registers), sum_b a_b and sum_b c_b, and two further exponentials in flight.  Its 2 spilled
+    #: SGPRs go to VGPR lanes, not to scratch.  On batches the kernel is bound by its instruction stream (DESIGN.md section
+    #: 10), which waves beyond the ones that cover the LDS broadcasts do not shorten (a tighter register bound was not tried).
+    #: The budget is what it compiles to, the 4-waves-per-SIMD one: 128 VGPRs, and no scratch at all.
+    #: k_members_finish (twelve outer trapezoids and their previous terms) is 78 VGPRs at 6 waves
+    max_vgpr=128, min_waves=4, extra_headers=("common/last_error.h",))
+
 #: the six libraries the shared builder started with (tests/test_side_libraries_cpu.py pins this tuple to exactly these)
 ALL = (CLUSTER, NESTED, SOLVE, DIAG, DERIVED, PREDICT)
 #: what __graft_entry__.build() and the command line below build, in order: ALL and the libraries added since ALL was
@@ -318,8 +337,8 @@ NEWER = (SELECT, REWEIGHT, RELATION, BINNED)
 #: the libraries added after NEWER was pinned in its turn (tests/test_side_libraries_cpu.py names its members);
 #: __graft_entry__.build() and the command line below go through BUILD_ORDER + ADDED + NEWER + LATEST.  The next library goes
 #: here: tests/test_shrink_library.py asserts membership, not equality, so this tuple grows (tests/test_emfit_library.py pins
-#: EMFIT as its fourth member)
-LATEST = (SHRINK, DRAW, BINFIT, EMFIT)
+#: EMFIT as its fourth member, tests/test_members_library.py MEMBERS as its fifth)
+LATEST = (SHRINK, DRAW, BINFIT, EMFIT, MEMBERS)
 
 
 if __name__ == "__main__":
