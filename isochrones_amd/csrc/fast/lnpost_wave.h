@@ -27,6 +27,11 @@
 // sample and walk star 0 / 1 / 2; row 3 only helps with the gathers.  The three stars' chains were the whole of a triple's
 // half-step (round 5: 55 us per step of a 9-band triple against 20 for the binary); side by side they cost one chain and
 // two exchanges across the rows (v_permlane16_swap + v_permlane32_swap, three vector instructions per dword).
+// bit 6 of LANE (the one-band single-star batch kernels, which sit at the 80 registers of six waves per SIMD): the three
+// parameters behind the stars' own (p[NS + 1 .. NS + 3]: [Fe/H], distance, A_V) wait out the model gather in the lane's
+// gather slot instead of in registers - doubles 6..8 of a slot are used by no request and no response (coop_gather.h) - and are
+// read back with the gathered columns; the parallax term reads the distance once more.  Six registers fewer across the
+// gather: with the caller's late output index (k_lnpost_fast) the kernel needs no scratch.  The same numbers, bit for bit.
 // Bands up to which the BC gather is taken lane-per-sample where LANE asks for it.  Measured per step of one star's fit
 // (tools/single_fit_shapes.py, profiles/r04/lane_bc_cap_ab.jsonl; 256 walkers): 1 band 8.97 us against 9.67 cooperative;
 // 2 / 3 / 4 bands 10.08 / 10.58 / 11.63 against 9.35 / 9.67 / 9.93; lifted to 8 bands: 5 / 6 / 8 bands 12.6 / 13.8 / 22.6
@@ -45,7 +50,10 @@ __device__ __forceinline__ double lnpost_wave(const FastArgs& A, const double* l
     // MP: the block the mass / age / [Fe/H] / A_V priors and the EEP bounds are read from - the sample's own block M, or
     // (catalogs whose stars share them: FastArgs.shared_priors) the first star's; observations and the distance prior
     // are always M's
-    const double q1 = p[NS], feh_par = p[NS + 1], dist = p[NS + 2], AV = p[NS + 3];
+    constexpr bool STASH = (LANE & 64) != 0;
+    static_assert(!STASH || (NS == 1 && NB <= 6 && !TILED && (LANE & (1 | 16 | 32)) == 0),
+                  "parameters in the gather slot: doubles 6..8 are free up to six bands; cooperative model gather");
+    double q1 = p[NS], feh_par = p[NS + 1], dist = p[NS + 2], AV = p[NS + 3];
 
     // ---- model table: axes 0/1 are shared by all components of an isochrone system ----
     const double x0 = (KIND == ISO_KIND_TRACK) ? p[2] : q1;        // feh | age
@@ -57,6 +65,12 @@ __device__ __forceinline__ double lnpost_wave(const FastArgs& A, const double* l
     W3 w;
     w.t2 = 0.0;
     lds_bracket2(lds, A.m0, A.m1, x0, x1, i0, i1, w.t0, w.t1);
+    double* const stash = L.req + L.lane * L.stride + 6;          // (STASH) doubles 6..8 of the lane's own slot
+    if constexpr (STASH) {
+        stash[0] = feh_par;
+        stash[1] = dist;
+        stash[2] = AV;
+    }
     // the prior terms that need nothing from the tables: evaluated either right after the gathers (as written in the
     // reference, starmodel.py:1616-1635) or, where a lone workgroup would only wait, while the primary's cell is on its way;
     // added up further down in the reference's order either way, so the sum is the same number
@@ -122,6 +136,12 @@ __device__ __forceinline__ double lnpost_wave(const FastArgs& A, const double* l
                 else coop_pair(A.astq, L, ok && M.has_numax, cell, w, astero);
             }
         }
+    }
+
+    if constexpr (STASH) {           // (behind the gather's last wave barrier: issued right after the reads of its response)
+        feh_par = stash[0];
+        dist = stash[1];
+        AV = stash[2];
     }
 
     // ---- lnprior ----
@@ -333,6 +353,7 @@ __device__ __forceinline__ double lnpost_wave(const FastArgs& A, const double* l
         if constexpr (PLX_EARLY) {
             lnl += plx_term;
         } else {
+            if constexpr (STASH) dist = stash[1];      // (not held across the BC gather for a term most models do not have)
             const double r = M.plx_val - 1000.0 / dist;
             lnl += M.plx_g0 - r * r * M.plx_hinv;
         }
@@ -374,8 +395,31 @@ __device__ __forceinline__ CoopLds coop_lds(double* lds, int axes_len)
     return L;
 }
 
+// The axes blob into LDS, for the batch kernels: the loads of up to four trips of the workgroup over the blob are in flight
+// before the first is written (the plain loop - one load, its wait, one write per trip - puts as many memory latencies one
+// behind the other as the blob has multiples of BLOCK doubles, at the head of every workgroup and, for the first workgroups
+// of a launch, with nothing else on the chip to hide them).  A trip past the end copies the last double onto itself once
+// more (every lane that does writes the same value): no branch between the loads, none between the writes.
+__device__ __forceinline__ void stage_axes(double* lds, const FastArgs& A)
+{
+    const int len = A.axes_len;
+    const double* __restrict__ blob = A.axes_blob;
+    for (int j0 = threadIdx.x; j0 < len; j0 += 4 * BLOCK) {
+        int j[4];
+        double v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            j[k] = min(j0 + k * BLOCK, len - 1);
+            v[k] = blob[j[k]];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) lds[j[k]] = v[k];
+    }
+}
+
 // waves per SIMD the register allocator must leave room for: 6 for the small single-star kernels
-// (88 -> 80 VGPR, a few dwords of scratch; measured +2 %), otherwise whatever the kernel needs
+// (88 -> 80 VGPR, a few dwords of scratch; measured +2 % - and since the one-band kernels keep three parameters in their
+// gather slot, k_lnpost_fast below, without the scratch: another 3.5 %), otherwise whatever the kernel needs
 // Multiple systems with many bands: the blanket 4-wave cap of rounds 1-3 held them to 128 registers and 288-364 B of
 // scratch per lane.  tools/sweep_fast_waves.py built the two- and three-star kernels for 2, 3 and 4 waves and timed every
 // (stars, bands) shape on 10^6-row batches, memory-bound and posterior-like (profiles/r04/fast_waves_*.jsonl): no
@@ -404,13 +448,11 @@ template <int KIND, int NS>
 __global__ __launch_bounds__(BLOCK, 4) void k_lnpost_wide(const FastArgs A)
 {
     extern __shared__ double lds[];
-    for (int j = threadIdx.x; j < A.axes_len; j += BLOCK) lds[j] = A.axes_blob[j];
-    __syncthreads();
-    const CoopLds L = coop_lds<WIDE_TILE>(lds, A.axes_len);
+    // the sample's parameters are asked for first: they depend on nothing that is staged, and their latency then runs under
+    // the staging of the axes instead of behind its barrier
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     const bool active = i < A.n;
     const int64_t ii = active ? i : (A.n - 1);
-    const DevModel& M = A.m[0];
     constexpr int NP = NS + 4;
     double p[NP];
     {
@@ -418,6 +460,10 @@ __global__ __launch_bounds__(BLOCK, 4) void k_lnpost_wide(const FastArgs A)
 #pragma unroll
         for (int j = 0; j < NP; ++j) p[j] = src[j * A.stride_p];
     }
+    stage_axes(lds, A);
+    __syncthreads();
+    const CoopLds L = coop_lds<WIDE_TILE>(lds, A.axes_len);
+    const DevModel& M = A.m[0];
     double lnp, lnl;
     const double r = lnpost_wave<KIND, NS, wide_tile(NS), false, false, true>(A, lds, L, active, M, p, A.lnlike != nullptr, lnp, lnl);
     if (active) {
@@ -443,27 +489,41 @@ __global__ __launch_bounds__(BLOCK, ASTERO ? (fast_min_waves(NS, NB) > 5 ? 5 : f
 void k_lnpost_fast(const FastArgs A)
 {
     extern __shared__ double lds[];
-    for (int j = threadIdx.x; j < A.axes_len; j += BLOCK) lds[j] = A.axes_blob[j];
-    __syncthreads();
-    const CoopLds L = coop_lds<NB>(lds, A.axes_len);
+    // the sample's parameters (and the row's star) are asked for first: they depend on nothing that is staged, and their
+    // latency then runs under the staging of the axes instead of behind its barrier
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     const bool active = i < A.n;
     const int64_t ii = active ? i : (A.n - 1);         // inactive lanes shadow the last sample
-    const DevModel& M = A.m[MULTI ? A.star_id[ii] : 0];
     constexpr int NP = NS + 4;
     double p[NP];
+    int star = 0;
     {
         const double* __restrict__ src = A.pars + ii * A.stride_n;
 #pragma unroll
         for (int j = 0; j < NP; ++j) p[j] = src[j * A.stride_p];
+        if constexpr (MULTI) star = A.star_id[ii];
     }
+    stage_axes(lds, A);
+    __syncthreads();
+    const CoopLds L = coop_lds<NB>(lds, A.axes_len);
+    const DevModel& M = A.m[star];
     double lnp, lnl;
     const DevModel& MP = (MULTI && A.shared_priors) ? A.m[0] : M;
-    const double r = lnpost_wave<KIND, NS, NB, ASTERO, MULTI>(A, lds, L, active, M, MP, p, A.lnlike != nullptr, lnp, lnl);
-    if (active) {
-        if (A.lnpost) A.lnpost[i] = r;
-        if (A.lnprior) A.lnprior[i] = lnp;
-        if (A.lnlike) A.lnlike[i] = lnl;
+    // the two one-band single-star kernels sit at the 80 registers of six waves per SIMD: three of their parameters wait out
+    // the model gather in the lane's slot (lnpost_wave's LANE bit 6)
+    constexpr bool SLIM = NS == 1 && NB == 1 && !MULTI && !ASTERO;
+    const double r = lnpost_wave<KIND, NS, NB, ASTERO, MULTI, false, false, SLIM ? 64 : 0>(A, lds, L, active, M, MP, p, A.lnlike != nullptr,
+                                                                                         lnp, lnl);
+    // the row index is formed again for the stores instead of being kept from the loads: two registers fewer through both
+    // gathers (the empty asm hides the lane from common-subexpression elimination, which would keep the first index alive).
+    // In the two kernels above this and the slot form together leave no scratch; each alone leaves a spill.
+    int t = L.lane;
+    asm volatile("" : "+v"(t));
+    const int64_t io = (int64_t)blockIdx.x * BLOCK + (__builtin_amdgcn_readfirstlane(threadIdx.x) & ~63) + t;
+    if (io < A.n) {
+        if (A.lnpost) A.lnpost[io] = r;
+        if (A.lnprior) A.lnprior[io] = lnp;
+        if (A.lnlike) A.lnlike[io] = lnl;
     }
     if (A.done_flag) {               // single-workgroup host-callback launch: results first, then the flag
         __threadfence_system();

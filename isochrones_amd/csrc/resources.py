@@ -81,9 +81,19 @@ SCRATCH_BUDGET = {
 }
 DEFAULT_SCRATCH = 0
 MAX_AGPR = 0
+#: limits of single kernels, tighter than their family's: {kernel: {"scratch": bytes per lane, "vgpr": registers}}.
+KERNEL_LIMITS = {
+    # the headline kernel and its isochrone twin: six waves per SIMD (80 registers) WITHOUT scratch.  Their 12 B per lane were
+    # 8 MB of spill stores per 10^6-row launch on top of an 8 MB result, through an L2 that keeps nothing for 5 us (DESIGN
+    # section 9); three parameters wait out the model gather in the lane's gather slot and the row index is formed again
+    # for the stores (fast/lnpost_wave.h).  A change that brings a spill back fails the build here.
+    "k_lnpost_fast<0, 1, 1, false, false>": {"scratch": 0, "vgpr": 80},
+    "k_lnpost_fast<1, 1, 1, false, false>": {"scratch": 0, "vgpr": 80},
+}
 
 
-def violations(table: dict, scratch_budget=None, default_scratch=None, max_agpr=None) -> list:
+def violations(table: dict, scratch_budget=None, default_scratch=None, max_agpr=None, kernel_limits=None) -> list:
+    kl = KERNEL_LIMITS if kernel_limits is None else kernel_limits
     sb = SCRATCH_BUDGET if scratch_budget is None else scratch_budget
     ds = DEFAULT_SCRATCH if default_scratch is None else default_scratch
     ma = MAX_AGPR if max_agpr is None else max_agpr
@@ -94,6 +104,9 @@ def violations(table: dict, scratch_budget=None, default_scratch=None, max_agpr=
         lim = sb.get(family(name), ds)
         if r.get("scratch", 0) > lim:
             bad.append("%s: %d B/lane of scratch (budget of %s: %d)" % (name, r["scratch"], family(name), lim))
+        for field, most in sorted(kl.get(name, {}).items()):
+            if r.get(field, 0) > most:
+                bad.append("%s: %s = %d (this kernel's limit: %d)" % (name, field, r[field], most))
     return bad
 
 

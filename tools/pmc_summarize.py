@@ -87,6 +87,11 @@ def main():
             d["fabric_GBs_profiled"] = d["fabric_bytes"] / d["profiled_kernel_us"] / 1e3
         if c("SQ_INSTS_VALU") is not None and c("SQ_WAVES"):
             d["valu_insts_per_wave"] = c("SQ_INSTS_VALU") / c("SQ_WAVES")
+        # vector-memory instructions per wave, scratch included: a spill store / reload shows here as one more write / read
+        # than the kernel's own stores / loads
+        for k, name in (("SQ_INSTS_VMEM_WR", "vmem_wr_insts_per_wave"), ("SQ_INSTS_VMEM_RD", "vmem_rd_insts_per_wave")):
+            if c(k) is not None and c("SQ_WAVES"):
+                d[name] = c(k) / c("SQ_WAVES")
         if c("SQ_WAVE_CYCLES") is not None and c("SQ_WAIT_ANY") is not None:
             d["wave_wait_fraction"] = c("SQ_WAIT_ANY") / c("SQ_WAVE_CYCLES")
         if c("SQ_LDS_BANK_CONFLICT") is not None and c("SQ_LDS_IDX_ACTIVE"):
